@@ -46,7 +46,30 @@ def parse():
     ap.add_argument("--live-only", action="store_true", help="profiling aid: run only the live-render leg (32 x 128 x 512^2) and print its object")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("GVF_BENCH_STREAMS", "2")),
                     help="4D samples kept in flight by the timed loop, one HIP stream + workspace + output buffer each (1 = strictly serial)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's sample) as DIR/<name>.npy, for comparing two builds")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_ELEMS = 1 << 23          # 32 MB of float32 per dumped array: the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, color, num_rendered):
+    """What a caller of gvf_rast_forward_batched receives for one step: the frames (F, 3, S, S) fp32 and the per-frame instance counts.
+    Frames larger than DUMP_MAX_ELEMS are written as a fixed seeded sample of their elements (flat indices drawn with replacement, ascending), so that
+    two builds run with the same arguments can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = color.reshape(-1)
+    if flat.numel() <= DUMP_MAX_ELEMS:
+        np.save(os.path.join(out_dir, "color.npy"), color.cpu().numpy().astype(np.float32))
+    else:
+        idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+        np.save(os.path.join(out_dir, "color_sample.npy"), flat[idx.to(flat.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "num_rendered.npy"), num_rendered.cpu().numpy().astype(np.float64))
 
 
 def _morton_perm(xyz, bits=5):
@@ -856,6 +879,9 @@ def main():
     if every_step:                               # the last gathered batch holds this rank's last sample at its rank-major position
         b, k = (a.steps - 1) % nbuf, (a.steps - 1) % n_slots
         assert torch.equal(gathered[b].view(world, F, 3, S, S)[rank], work.R.frames_to_uint8(slots[k].color))
+    if a.dump_outputs and rank == 0:              # the slot that rendered the last timed step
+        k = (a.steps - 1) % n_slots
+        dump_outputs(a.dump_outputs, slots[k].color, slots[k].nr)
 
     t = torch.tensor([dt, dt_serial], dtype=torch.float64, device=dev if (not multi or dist.get_backend() == "nccl") else "cpu")
     if multi:

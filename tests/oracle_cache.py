@@ -4,7 +4,8 @@ the child process of test_kv_resident_attention_variant_forced_everywhere).
 
 A result is keyed by the sha1 of a tag, the oracle's source file, the configuration and the BYTES of every input tensor, so a hit is the same
 computation on the same data by the same oracle code; nothing about the device path is cached.  Files live under $GVF_TEST_CACHE (default
-<tmp>/gvf_oracle_cache), are shared by the processes of one run and harmless across runs.  GVF_TEST_CACHE=off disables the cache."""
+<tmp>/gvf_oracle_cache_<uid>), are shared by the processes of one run and harmless across runs.  GVF_TEST_CACHE=off disables the cache.
+The default is per user: on a shared machine another user's cache directory is not writable, and its files are not this user's results."""
 import hashlib
 import json
 import os
@@ -12,7 +13,7 @@ import tempfile
 
 import torch
 
-_DIR = os.environ.get("GVF_TEST_CACHE", os.path.join(tempfile.gettempdir(), "gvf_oracle_cache"))
+_DIR = os.environ.get("GVF_TEST_CACHE", os.path.join(tempfile.gettempdir(), f"gvf_oracle_cache_{os.getuid()}"))
 
 
 def _feed(h, obj):
