@@ -36,6 +36,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include "gvf_common.h"
 #include "gvf_sort.h"
@@ -62,14 +63,38 @@ constexpr int PRE_FB = GVF_PRE_FB;   // frames per preprocess workgroup: the fra
 #ifndef GVF_PRE_XCD
 #define GVF_PRE_XCD 0
 #endif
-// 1: preprocess_kernel<true> (the shared-activation launch) stores its splat records quad-transposed, whole 64-byte lines per instruction (see there);
-// the fused launch keeps three 16-byte stores per lane (the transposed form costs it 13 registers; 0.377 -> 0.368 ms, inside the noise)
+// 1: both preprocess launches store their splat records quad-transposed, whole 64-byte lines per instruction (see there).  The fused launch
+// took it once its bin records left as whole lines too: 283 -> 266 us per launch, 70 -> 83 registers, still 5 waves per SIMD (the SH staging
+// binds); before that its gain was inside the noise (0.377 -> 0.368 ms, round 5).  0: three 16-byte stores per lane in both.
 #ifndef GVF_PRE_REC_QUAD
 #define GVF_PRE_REC_QUAD 1
 #endif
 // 1: the delta row of frame ff + 1 is requested before frame ff's arithmetic (experiment; no gain: same file)
 #ifndef GVF_PRE_PREFETCH
 #define GVF_PRE_PREFETCH 0
+#endif
+// 1: preprocess_kernel<false> stages its workgroup's 256 delta rows (56 B each, one contiguous 14 KiB span per frame) through LDS with coalesced
+// 16-byte loads; the span of frame ff + 1 is loaded into registers before frame ff's arithmetic and written to LDS after it (one LDS buffer:
+// the rows move to registers first).  Experiment, not built by default and covered by no test there: the 14 KiB of LDS leave 3 workgroups per
+// CU instead of 5 at SH degree 2 (127 registers), and the launch is SLOWER, 283 -> 306 us (266 -> 296 us with the quad-transposed records;
+// profiles/r07_preprocess_forms_ab.txt).  The per-lane row gathers are not what holds the launch back once the stores are whole lines.
+#ifndef GVF_PRE_DELTA_LDS
+#define GVF_PRE_DELTA_LDS 0
+#endif
+// Bucket binning of the calls without shared activation (the fused launch preprocess_kernel<false>): where the bin records go and how the
+// count / scatter passes walk them.
+//   0: records stored at the Gaussian's Morton slot (a 16-byte store to an effectively random place in the frame's 4 MB per lane), the bin
+//      passes read them by slot as one stream (round 1-6 form).
+//   1: records stored at the Gaussian's own index (coalesced lines); bin_kernel gathers them by Morton order, each XCD taking whole frames so
+//      that a frame's 4 MB of records is gathered from its own L2.
+//   2: as 1, but the count pass is bin_index_kernel<false>: it walks the records in index order against a whole-frame LDS tile table.
+//   3: both passes in index order (bin_index_kernel), no Morton order for these calls.
+// Measured at the bench shape (one box, per launch): 0: preprocess 355 us, count 44, scatter 71, Morton launches 52; 1: preprocess 287,
+// count 67, scatter 95; 3: preprocess 286, count 32, scatter 222 (a workgroup's run per tile shrinks to ~11 keys); 2 takes the cheaper pass
+// of each (profiles/r07_bin_layout_ab.txt).  The default build runs 2 (and 0's layout on the shared-activation path); 1, 3 and with them
+// bin_index_kernel<true> are A/B switches, built only by `_build --variant` and covered by no test there.
+#ifndef GVF_BIN_ALGO
+#define GVF_BIN_ALGO 2
 #endif
 constexpr int TILE = GVF_TILE;
 constexpr int BLEND_THREADS = TILE * TILE;
@@ -133,6 +158,7 @@ struct PreParams {
     int n_delta;
     int upstream_binning;   // 1: bin the whole 3-sigma tile rect as upstream does
     int F;                  // frames of the call (grid.y covers them PRE_FB at a time)
+    int delta_lds;          // GVF_PRE_DELTA_LDS and the delta rows of a workgroup are whole 16-byte pieces (P even, 16-B aligned tensor)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -469,6 +495,33 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         for (int k = t; k < n4; k += PRE_THREADS) dst4[k] = src4[k];
         for (int k = (n4 << 2) + t; k < total; k += PRE_THREADS) sh_lds[k] = sh[span0 + k];
     }
+#if GVF_PRE_DELTA_LDS
+    // delta rows through LDS (pp.delta_lds: the span of a workgroup is nvalid * 14 floats, nvalid even, 16-byte aligned): dq 16-byte pieces per frame
+    float* d_lds = sh_lds + ((size_t)PRE_THREADS * sh_stride * 4 + 15) / 16 * 4 + 4;     // behind the SH rows (host: sh_lds_bytes)
+    const bool dstage = !SHARED && pp.delta_lds && pp.fused && delta != nullptr;
+    const int dq = min(PRE_THREADS, P - bx * PRE_THREADS) * 14 / 4;
+    float4 dreg0 = make_float4(0.f, 0.f, 0.f, 0.f), dreg1 = dreg0, dreg2 = dreg0, dreg3 = dreg0;
+    // the frame's delta slice (workgroup-uniform) -> the four pieces of this thread; false: the frame has none
+    auto dfetch = [&](int f_) -> bool {
+        const int di_ = frames[f_].delta_index;
+        if (di_ < 0) return false;
+        const float4* src = reinterpret_cast<const float4*>(delta + ((size_t)di_ * P + (size_t)bx * PRE_THREADS) * 14) + t;
+        if (t < dq) dreg0 = src[0];
+        if (t + PRE_THREADS < dq) dreg1 = src[PRE_THREADS];
+        if (t + 2 * PRE_THREADS < dq) dreg2 = src[2 * PRE_THREADS];
+        if (t + 3 * PRE_THREADS < dq) dreg3 = src[3 * PRE_THREADS];
+        return true;
+    };
+    auto dcommit = [&]() {
+        float4* dst = reinterpret_cast<float4*>(d_lds) + t;
+        if (t < dq) dst[0] = dreg0;
+        if (t + PRE_THREADS < dq) dst[PRE_THREADS] = dreg1;
+        if (t + 2 * PRE_THREADS < dq) dst[2 * PRE_THREADS] = dreg2;
+        if (t + 3 * PRE_THREADS < dq) dst[3 * PRE_THREADS] = dreg3;
+    };
+    bool dcur = false;
+    if (dstage && by * PRE_FB < pp.F) { dcur = dfetch(by * PRE_FB); if (dcur) dcommit(); }
+#endif
     __syncthreads();
 
   const uint32_t my_slot = (bin_slot != nullptr && i < P) ? bin_slot[i] : (uint32_t)i;
@@ -498,6 +551,23 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     const int f = by * PRE_FB + ff;
     if (f >= pp.F) break;
     const GvfRastFrame* fr = frames + f;
+#if GVF_PRE_DELTA_LDS
+    float drow[14];
+    if (dstage) {
+        if (dcur && i < P) {
+#pragma unroll
+            for (int k = 0; k < 14; ++k) drow[k] = d_lds[t * 14 + k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < 14; ++k) drow[k] = 0.0f;
+        }
+    }
+    bool dnext = false;
+    if (dstage && ff + 1 < PRE_FB && f + 1 < pp.F) {      // uniform
+        __syncthreads();                                  // every row of frame ff has left the buffer
+        dnext = dfetch(f + 1);                            // in flight during this frame's arithmetic
+    }
+#endif
 #if GVF_PRE_PREFETCH
     float dcur[14];
 #pragma unroll
@@ -522,6 +592,16 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         } else if (pp.fused) {
 #if GVF_PRE_PREFETCH
             ActGaussian g = activate_vals(i, pp.act, a0, a1, a2, a3, dcur, dcur_has);
+#elif GVF_PRE_DELTA_LDS
+            bool dhas = dcur;
+            if (!dstage) {                                // the row straight from global memory (activate_one's form)
+                const int di = fr->delta_index;
+                const float* d = (delta != nullptr && di >= 0) ? delta + ((size_t)di * P + i) * 14 : nullptr;
+#pragma unroll
+                for (int k = 0; k < 14; ++k) drow[k] = d ? d[k] : 0.0f;
+                dhas = d != nullptr;
+            }
+            ActGaussian g = activate_vals(i, pp.act, a0, a1, a2, a3, drow, dhas);
 #else
             const int di = fr->delta_index;
             const float* d = (delta != nullptr && di >= 0) ? delta + ((size_t)di * P + i) * 14 : nullptr;
@@ -643,7 +723,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
 #if defined(PRE_ABL_NOREC)      // timing experiment: no record stores (one dword keeps the arithmetic alive)
         if (touched != 0 && gA.x == 12345.678f) splats[4 * o] = gA;
 #else
-        if (!(GVF_PRE_REC_QUAD && SHARED) && touched != 0) {   // records of culled Gaussians are never read (no instance refers to them)
+        if (!GVF_PRE_REC_QUAD && touched != 0) {   // records of culled Gaussians are never read (no instance refers to them)
             float4* rec = splats + 4 * o;
             rec[0] = gA; rec[1] = gB; rec[2] = gC;
         }
@@ -664,9 +744,6 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
             }
 #if defined(PRE_ABL_NOBIN)      // timing experiment: no bin-record stores
             if (gC.y == 12345.678f)
-#elif defined(PRE_ABL_BINLINEAR) // timing experiment: bin records at the Gaussian's own index (coalesced) instead of its Morton slot
-            binrec[(size_t)f * P + i] = make_uint4((uint32_t)rect.x0 | ((uint32_t)rect.y0 << 16), (uint32_t)rect.x1 | ((uint32_t)rect.y1 << 16), __float_as_uint(gC.y), slab);
-            if (false)
 #endif
             binrec[(size_t)f * P + my_slot] = make_uint4((uint32_t)rect.x0 | ((uint32_t)rect.y0 << 16),
                                                          (uint32_t)rect.x1 | ((uint32_t)rect.y1 << 16), __float_as_uint(gC.y), slab);
@@ -674,8 +751,8 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     }
 
 #if !defined(PRE_ABL_NOREC)
-    if (GVF_PRE_REC_QUAD && SHARED) {
-        // Quad-transposed record store (shared-activation launch): lane 4 g + j writes piece j (16 bytes; piece 3 = the padding) of the records of lanes
+    if (GVF_PRE_REC_QUAD) {
+        // Quad-transposed record store: lane 4 g + j writes piece j (16 bytes; piece 3 = the padding) of the records of lanes
         // 4 g + k, k = 0 .. 3, so ONE instruction stores 16 whole 64-byte lines where the per-lane form stores 64 quarter lines three times (48 of a
         // line's 64 bytes, masked at the memory side).  The launch is bound by its stores (no record stores: -26 %, no bin-record stores: -21 %,
         // profiles/r05_preprocess_store_ablation.txt); this form: live job 146-148 -> 141-142 ms per sample.  All 64 lanes run it (a lane past P or
@@ -709,6 +786,10 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         __syncthreads();
         if (t == 0) block_sums[(size_t)f * nbx + bx] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     }
+#if GVF_PRE_DELTA_LDS
+    if (dnext) { dcommit(); __syncthreads(); }            // uniform; the next frame reads the buffer
+    dcur = dnext;
+#endif
   }
 }
 
@@ -923,10 +1004,12 @@ __global__ void frame_zrange_kernel(const GvfRastFrame* __restrict__ frames, int
 }
 
 // Count / scatter passes over the compact bin records, BIN_SPT slots per thread, slots taken in Morton order
-// (`order` = the Gaussian of each slot, may be null = identity; the records themselves are stored by slot): the rects of one block then fall into a small window of tiles, instances are
+// (`order` = the Gaussian of each slot, may be null = identity): the rects of one block then fall into a small window of tiles, instances are
 // counted in an LDS table and every touched tile costs ONE global atomic per block (count pass: += tile_count;
 // scatter pass: cursor allocation, the base is left in the table and an LDS counter hands out the slots).  A block
 // whose window exceeds WIN_MAX tiles (incoherent order) pays one global atomic per instance instead.
+// rec_by_id = 0: the records sit at their slots (preprocess_kernel's bin_slot) and are read as one stream; 1: they sit at the Gaussian's index
+// and are gathered (GVF_BIN_ALGO 1-3), and xcd_frames = 1 then lays the grid out 1-D so that each XCD takes whole frames (see the host).
 constexpr int WIN_MAX = 2048;
 constexpr int BIN_SPT = 4;
 constexpr int BIN_SLOTS = PRE_THREADS * BIN_SPT;
@@ -938,26 +1021,37 @@ __global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy,
                                                           uint32_t* __restrict__ cursor /* scatter pass */,
                                                           const uint32_t* __restrict__ total,
                                                           uint64_t* __restrict__ payload, int nslab,
-                                                          const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ num_rendered) {
+                                                          const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ num_rendered,
+                                                          int rec_by_id, int xcd_frames, int F) {
     __shared__ uint32_t s_tab[WIN_MAX];
     __shared__ uint32_t s_run[SCATTER ? WIN_MAX : 1];
     __shared__ int s_box[4];
+    int blk = (int)blockIdx.x, f = (int)blockIdx.y;
+    if (xcd_frames) {
+        // frame 8 g + n % 8 of frame group g, block (n / 8) % nblk of it: every (frame, block) exactly once.  A performance heuristic, measured
+        // (scatter pass 95 us with it at the bench shape), not derived: it assumes the dispatcher hands workgroup n to XCD n % 8, so that one
+        // XCD gathers a frame's records from its own L2; another dispatch order costs only speed.
+        const int nblk = (P + BIN_SLOTS - 1) / BIN_SLOTS, k = (int)(blockIdx.x >> 3);
+        f = (k / nblk) * 8 + (int)(blockIdx.x & 7u);
+        blk = k - (k / nblk) * nblk;
+        if (f >= F) return;                          // the grid is rounded up to whole groups of 8 frames (workgroup-uniform)
+    }
     // scatter pass: the per-frame instance counts from the frame bases the scan left (saves a launch of its own)
-    if (SCATTER && num_rendered != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
-        num_rendered[blockIdx.y] = frame_base[blockIdx.y + 1] - frame_base[blockIdx.y];
+    if (SCATTER && num_rendered != nullptr && blk == 0 && threadIdx.x == 0)
+        num_rendered[f] = frame_base[f + 1] - frame_base[f];
     if (SCATTER && *total == 0u) return;            // nothing visible, or capacity overflow (uniform)
-    const int t = threadIdx.x, lane = t & 63, f = blockIdx.y;
+    const int t = threadIdx.x, lane = t & 63;
     if (t == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0x7fffffff; s_box[2] = 0; s_box[3] = 0; }
     int x0[BIN_SPT], y0[BIN_SPT], x1[BIN_SPT], y1[BIN_SPT], sl[BIN_SPT];
     uint64_t key[BIN_SPT];
     int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = 0, by1 = 0;
 #pragma unroll
     for (int k = 0; k < BIN_SPT; ++k) {
-        const int s = blockIdx.x * BIN_SLOTS + k * PRE_THREADS + t;
+        const int s = blk * BIN_SLOTS + k * PRE_THREADS + t;
         x0[k] = y0[k] = x1[k] = y1[k] = 0; sl[k] = 0; key[k] = 0;
         if (s < P) {
             const uint32_t id = order != nullptr ? order[s] : (uint32_t)s;
-            const uint4 br = binrec[(size_t)f * P + s];                // records sit at their slots (preprocess_kernel, bin_slot)
+            const uint4 br = binrec[(size_t)f * P + (rec_by_id ? id : (uint32_t)s)];
             x0[k] = (int)(br.x & 0xffffu); y0[k] = (int)(br.x >> 16);
             x1[k] = (int)(br.y & 0xffffu); y1[k] = (int)(br.y >> 16);
             sl[k] = (int)br.w;
@@ -1018,6 +1112,72 @@ __global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy,
                     const uint32_t pos = atomicAdd(&gtab[(y * gx + x) * nslab + sl[k]], 1u);
                     if (SCATTER) payload[pos] = key[k];
                 }
+    }
+}
+
+// Count / scatter passes in index order (GVF_BIN_ALGO 2): a workgroup takes BINX_PER_WG consecutive Gaussians of one frame, whose bin records
+// preprocess_kernel<false> stored at their own index, and counts their instances in a whole-frame LDS table of (tile, slab) segments, so
+// that every touched segment costs ONE global atomic per workgroup however the Gaussians are ordered in space.  The scatter pass counts
+// again, allocates each segment's run with that atomic and hands out the places from an LDS counter.  The host takes this path only when
+// the frame's segments fit the table (ntiles * nslab <= BINX_TAB).
+constexpr int BINX_THREADS = 512;
+constexpr int BINX_TAB = 4096;
+constexpr int BINX_PER_WG = 8192;
+constexpr int BINX_SPT = 4;                          // records in flight per thread
+
+template <bool SCATTER>
+__global__ __launch_bounds__(BINX_THREADS) void bin_index_kernel(int P, int gx, const uint4* __restrict__ binrec,
+                                                                 uint32_t* __restrict__ tile_count /* count pass */,
+                                                                 uint32_t* __restrict__ cursor /* scatter pass */,
+                                                                 const uint32_t* __restrict__ total,
+                                                                 uint64_t* __restrict__ payload, int nslab, int nseg_frame,
+                                                                 const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ num_rendered) {
+    __shared__ uint32_t s_tab[BINX_TAB];
+    __shared__ uint32_t s_run[SCATTER ? BINX_TAB : 1];
+    const int t = threadIdx.x, f = blockIdx.y;
+    if (SCATTER && num_rendered != nullptr && blockIdx.x == 0 && t == 0) num_rendered[f] = frame_base[f + 1] - frame_base[f];
+    if (SCATTER && *total == 0u) return;            // nothing visible, or capacity overflow (uniform)
+    const int g0 = (int)blockIdx.x * BINX_PER_WG, g1 = min(P, g0 + BINX_PER_WG);
+    const uint4* rec = binrec + (size_t)f * P;
+    for (int e = t; e < nseg_frame; e += BINX_THREADS) { s_tab[e] = 0u; if (SCATTER) s_run[e] = 0u; }
+    __syncthreads();
+    // one sweep over the workgroup's records: PASS 0 counts into s_tab, PASS 1 (scatter) writes the keys at s_tab[e] + run
+    auto sweep = [&](auto pass) {
+        for (int base = g0; base < g1; base += BINX_SPT * BINX_THREADS) {
+            uint4 br[BINX_SPT];
+#pragma unroll
+            for (int k = 0; k < BINX_SPT; ++k) {
+                const int s = base + k * BINX_THREADS + t;
+                br[k] = s < g1 ? rec[s] : make_uint4(0u, 0u, 0u, 0u);     // {0, 0, 0, 0}: an empty rect
+            }
+#pragma unroll
+            for (int k = 0; k < BINX_SPT; ++k) {
+                const int x0 = (int)(br[k].x & 0xffffu), y0 = (int)(br[k].x >> 16);
+                const int x1 = (int)(br[k].y & 0xffffu), y1 = (int)(br[k].y >> 16);
+                const int sl = (int)br[k].w;
+                const uint64_t key = ((uint64_t)br[k].z << 32) | (uint32_t)(base + k * BINX_THREADS + t);   // depth bits above the Gaussian id
+                for (int y = y0; y < y1; ++y)
+                    for (int x = x0; x < x1; ++x) {
+                        const int e = (y * gx + x) * nslab + sl;
+                        if constexpr (decltype(pass)::value == 0) atomicAdd(&s_tab[e], 1u);
+                        else payload[s_tab[e] + atomicAdd(&s_run[e], 1u)] = key;
+                    }
+            }
+        }
+    };
+    sweep(std::integral_constant<int, 0>{});
+    __syncthreads();
+    uint32_t* gtab = (SCATTER ? cursor : tile_count) + (size_t)f * nseg_frame;   // [tile][slab]
+    for (int e = t; e < nseg_frame; e += BINX_THREADS) {
+        const uint32_t c = s_tab[e];
+        if (c != 0u) {
+            if (SCATTER) s_tab[e] = atomicAdd(&gtab[e], c);
+            else atomicAdd(&gtab[e], c);
+        }
+    }
+    if (SCATTER) {
+        __syncthreads();
+        sweep(std::integral_constant<int, 1>{});
     }
 }
 
@@ -1101,8 +1261,8 @@ __global__ __launch_bounds__(1024) void morton_scan_kernel(uint32_t* __restrict_
     for (int k = 0; k < PER; ++k) { hist[t * PER + k] = run; run += v[k]; }
 }
 
-// codes_rank: in = the Gaussian's Morton code, out = its slot in the order (the inverse permutation: preprocess writes the bin
-// records at their slots, so the bin passes read them as one contiguous stream instead of gathering a 64-byte line per 16-byte record)
+// codes_rank: in = the Gaussian's Morton code, out = its slot in the order (the inverse permutation: the shared-activation launch, and
+// the fused one under GVF_BIN_ALGO 0, write the bin records at their slots, so the bin passes read them as one contiguous stream)
 __global__ __launch_bounds__(256) void morton_scatter_kernel(int P, uint32_t* codes_rank, uint32_t* __restrict__ hist,
                                                              uint32_t* __restrict__ order) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2076,7 +2236,6 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
     int slot = g_prof.on ? g_prof.calls.fetch_add(1) : -1;
     if (slot >= PROF_MAX_CALLS) slot = -1;
 
-    const bool morton = st.bin_algo != GVF_RAST_BIN_RADIX && F >= 4 && P >= 4096;     // spatial order of the Gaussians (see below)
     // ---- shared activation (activate_cov_kernel): the call's distinct delta slices, if they are few.  The records live in keys_alt, which only
     // the radix binning uses (max_rendered x 8 bytes: room for max_rendered / (8 P) slices; a sizing call with max_rendered = 0 takes the fused path,
     // whose outputs are the same bits).  GVF_RAST_SHARED_ACT=0: measurement / test switch.
@@ -2100,6 +2259,11 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         // worth it from two frames per slice on; the records must fit into keys_alt
         if (shared && (F < 2 * slices.n || (size_t)slices.n * (size_t)P * 64u > (size_t)(max_rendered > 0 ? max_rendered : 0) * 8u)) shared = false;
     }
+    // bucket binning without shared activation (GVF_BIN_ALGO): bin_index_kernel takes the count pass (2, 3) and the scatter pass (3) when a
+    // frame's (tile, slab) segments fit its table
+    const bool index_fits = st.bin_algo != GVF_RAST_BIN_RADIX && !shared && (size_t)ntiles * NSLAB <= (size_t)BINX_TAB;
+    const bool index_count = GVF_BIN_ALGO >= 2 && index_fits, index_scatter = GVF_BIN_ALGO == 3 && index_fits;
+    const bool morton = st.bin_algo != GVF_RAST_BIN_RADIX && F >= 4 && P >= 4096 && !index_scatter;   // spatial order of the Gaussians (see below)
     for (int f0 = 0; f0 < F; f0 += 16) {
         FrameChunk ch;
         const int cnt = F - f0 < 16 ? F - f0 : 16;
@@ -2146,6 +2310,8 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         }
         // depth slabs need the scene's depth range, which comes with the Morton stage: one slab otherwise
         const int nslab = order != nullptr ? NSLAB : 1;
+        // GVF_BIN_ALGO 1-3: preprocess_kernel<false> stores the bin records at the Gaussians' indices, bin_kernel gathers them in Morton order
+        const bool rec_gather = GVF_BIN_ALGO >= 1 && bucket && !shared && order != nullptr;
         nslab_blend = nslab;
         const unsigned nseg = (unsigned)((size_t)F * ntiles * nslab);
         prof_mark(stream, slot, 1);
@@ -2157,6 +2323,8 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         pp.upstream_binning = (st.upstream_binning != 0 || subpixel_offset != nullptr) ? 1 : 0;
         if (fused) pp.act = *act; else pp.act = GvfGaussianActivation{};
         const size_t sh_lds_bytes = gvf_align_up((size_t)PRE_THREADS * pp.M * 3 * sizeof(float), 16) + 16;
+        pp.delta_lds = (GVF_PRE_DELTA_LDS && fused && delta != nullptr && P % 2 == 0 && (((uintptr_t)delta) & 15) == 0) ? 1 : 0;
+        const size_t pre_lds_bytes = sh_lds_bytes + (pp.delta_lds ? (size_t)PRE_THREADS * 14 * sizeof(float) : 0);   // + the delta rows
         const int pre_fy = (F + PRE_FB - 1) / PRE_FB;
         const dim3 pre_grid = GVF_PRE_XCD ? dim3((nb + 7) / 8 * 8 * pre_fy) : dim3(nb, pre_fy);
         if (shared) {
@@ -2185,15 +2353,22 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
                                nullptr, nullptr, w.splats, nullptr, out_radii == nullptr ? nullptr : w.radii, nullptr, w.binrec,
                                order != nullptr ? w.order_alt : nullptr, nslab > 1 ? w.zrange : nullptr);
         } else
-        hipLaunchKernelGGL(preprocess_kernel<false>, pre_grid, dim3(PRE_THREADS), sh_lds_bytes, stream, pp,
+        hipLaunchKernelGGL(preprocess_kernel<false>, pre_grid, dim3(PRE_THREADS), pre_lds_bytes, stream, pp,
                            w.frames, a0, a1, a2, a3, colors_precomp ? nullptr : sh, colors_precomp, cov3D_precomp, delta,
                            w.splats, bucket ? nullptr : w.tiles_touched, (bucket && out_radii == nullptr) ? nullptr : w.radii,
-                           bucket ? nullptr : w.block_sums, bucket ? w.binrec : nullptr, order != nullptr ? w.order_alt : nullptr,
-                           (bucket && nslab > 1) ? w.zrange : nullptr);
-        const int bnb = (P + BIN_SLOTS - 1) / BIN_SLOTS;
-        if (bucket)
-            hipLaunchKernelGGL(bin_kernel<false>, dim3(bnb, F), dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
-                               w.tile_count, w.cursor, w.total, w.keys, nslab, nullptr, nullptr);
+                           bucket ? nullptr : w.block_sums, bucket ? w.binrec : nullptr,
+                           (order != nullptr && !rec_gather) ? w.order_alt : nullptr, (bucket && nslab > 1) ? w.zrange : nullptr);
+        // bin passes: index order (bin_index_kernel), or Morton order over records at their slots / gathered from the Gaussians' indices,
+        // the gather with a 1-D grid in which each XCD takes whole frames (bin_kernel).  The count pass only sums per segment, so its walk
+        // need not be the scatter pass's.
+        const int bnb = (P + BIN_SLOTS - 1) / BIN_SLOTS, xnb = (P + BINX_PER_WG - 1) / BINX_PER_WG;
+        const dim3 bin_grid = rec_gather ? dim3((unsigned)((F + 7) / 8 * 8 * bnb)) : dim3(bnb, F);
+        if (index_count)
+            hipLaunchKernelGGL(bin_index_kernel<false>, dim3(xnb, F), dim3(BINX_THREADS), 0, stream, P, gx, w.binrec,
+                               w.tile_count, w.cursor, w.total, w.keys, nslab, ntiles * nslab, nullptr, nullptr);
+        else if (bucket)
+            hipLaunchKernelGGL(bin_kernel<false>, bin_grid, dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
+                               w.tile_count, w.cursor, w.total, w.keys, nslab, nullptr, nullptr, rec_gather ? 1 : 0, rec_gather ? 1 : 0, F);
         GVF_CHECK_LAUNCH();
         prof_mark(stream, slot, 2);
         if (bucket)
@@ -2212,9 +2387,13 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         GVF_CHECK_LAUNCH();
         prof_mark(stream, slot, 3);
         if (max_rendered > 0) {
-            if (bucket)
-                hipLaunchKernelGGL(bin_kernel<true>, dim3(bnb, F), dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
-                                   w.tile_count, w.cursor, w.total, w.keys, nslab, w.frame_base, out_num_rendered);
+            if (index_scatter)
+                hipLaunchKernelGGL(bin_index_kernel<true>, dim3(xnb, F), dim3(BINX_THREADS), 0, stream, P, gx, w.binrec,
+                                   w.tile_count, w.cursor, w.total, w.keys, nslab, ntiles * nslab, w.frame_base, out_num_rendered);
+            else if (bucket)
+                hipLaunchKernelGGL(bin_kernel<true>, bin_grid, dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
+                                   w.tile_count, w.cursor, w.total, w.keys, nslab, w.frame_base, out_num_rendered,
+                                   rec_gather ? 1 : 0, rec_gather ? 1 : 0, F);
             else
                 hipLaunchKernelGGL(duplicate_kernel, dim3(nb, F), dim3(PRE_THREADS), 0, stream, P, gx, gy, w.splats,
                                    w.tiles_touched, w.radii, w.block_sums, w.keys, w.vals, (uint32_t)max_rendered,
