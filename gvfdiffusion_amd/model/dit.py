@@ -35,6 +35,16 @@ _CAPTURE_LOCK = __import__("threading").Lock()      # hipGraph captures of DiT i
 _CTX_EPOCHS = __import__("itertools").count(1)      # names of the condition cache's buffer sets (DiT.prepare_conditions): a captured graph is keyed on one
 
 
+def _gemm_f32_any_batch(a, w, bias, out):
+    """out (fp32) = a w^T + bias on a kernel chosen from N, K and the strides alone, never from M (the batch).  gvf_gemm takes gvf_gemm8 only
+    from one tile per CU on; the two kernels give the same bits today (both chain 32-deep MFMA k-steps in ascending k, then add the bias:
+    tests/test_gemm_conformance_gpu.py::test_router_across_the_eight_wave_threshold), but neither promises it, and the condition products
+    must not depend on what a sample is batched with.  gvf_gemm8's fp32 store takes any M, so an eligible projection always runs on it."""
+    use8 = os.environ.get("GVF_GEMM8", "1") != "0" and \
+        dit_ops.gemm8_eligible(256, w.shape[0], a.shape[1], a.stride(0), w.stride(0), out.stride(0), dit_ops.EPI_STORE_F32) != 0
+    (dit_ops.gemm8 if use8 else dit_ops.gemm)(a, w, bias, out, dit_ops.EPI_STORE_F32)
+
+
 class AbsolutePositionEmbedder(nn.Module):
     """(B, L, in_channels) positions -> (B, L, channels): per axis [sin(x f_i), cos(x f_i)], zero-padded
     (model/dit.py:16-56).  Step-invariant, evaluated once per condition set with torch device ops."""
@@ -447,8 +457,9 @@ class DiT(nn.Module):
         # at fp32-class accuracy on the bf16 matrix pipe -- both operands as two-term bf16 expansions laid out along K (dit_ops.split3_bf16:
         # a w^T = a_hi w_hi^T + a_lo w_hi^T + a_hi w_lo^T + O(2^-16)), ONE plain gvf_gemm with fp32 accumulation and fp32 output per projection
         # (three products at the 16-bit MFMA rate against one at v_mfma_f32's sixteenth of it; rounds 2-4 called rocBLAS here: ~5 ms per
-        # sample).  Every output row is summed in one fixed order (no split-K), so a sample's numbers do not depend on what it is batched
-        # with (tests: batch of three == three single samples, bit for bit).  Then ONE rounding to 16 bits when the cache builder folds the
+        # sample).  Every output row is summed in one fixed order (no split-K, and the kernel is picked without looking at M:
+        # _gemm_f32_any_batch), so a sample's numbers do not depend on what it is batched with (tests: batch of three == three single
+        # samples, batch of eight == eight single samples, bit for bit).  Then ONE rounding to 16 bits when the cache builder folds the
         # softmax scale in and stores the tiled image the attention workgroups stage into LDS (csrc/attn_xt.hip); static K/V once per
         # sample, not per frame.
         H = self.num_heads
@@ -456,8 +467,8 @@ class DiT(nn.Module):
         f32 = torch.float32
         img_emb = torch.empty((B * Tc * Li, C), dtype=f32, device=dev)
         st_emb = torch.empty((B * Ls, C), dtype=f32, device=dev)
-        dit_ops.gemm(dit_ops.split3_bf16(cond_images.reshape(B * Tc * Li, Ci).float().contiguous()), S3["img"], W["img_f32"][1], img_emb, dit_ops.EPI_STORE_F32)
-        dit_ops.gemm(dit_ops.split3_bf16(static_latent.reshape(B * Ls, -1).float().contiguous()), S3["static"], W["static_f32"][1], st_emb, dit_ops.EPI_STORE_F32)
+        _gemm_f32_any_batch(dit_ops.split3_bf16(cond_images.reshape(B * Tc * Li, Ci).float().contiguous()), S3["img"], W["img_f32"][1], img_emb)
+        _gemm_f32_any_batch(dit_ops.split3_bf16(static_latent.reshape(B * Ls, -1).float().contiguous()), S3["static"], W["static_f32"][1], st_emb)
         # fp16 caches keep the 64 largest-norm keys of every (set, head) in the first tile (gvf_attn_key_order / gvf_attn_pack_kv_ordered): the kernel's per-query shift is the best
         # score against the FIRST key tile and a later key that beats it by 2^16 costs the workgroup an exact pass -- on trained-like scores
         # 38 % of the workgroups with the keys in context order, ~0 with the high-norm keys (attention sinks, artefact tokens) in front
@@ -495,8 +506,6 @@ class DiT(nn.Module):
         M = x3.shape[0]
         per_block = M * 2 * C * 4
         G = max(1, min(nb, int(os.environ.get("GVF_DIT_KV_CHUNK_BYTES", 2 << 30)) // max(per_block, 1)))       # (the variable: a measurement switch)
-        # the kernel is chosen from N and K alone, so that a sample's numbers do not depend on what it is batched with
-        g8 = lambda n_: os.environ.get("GVF_GEMM8", "1") != "0" and dit_ops.gemm8_eligible(256, n_, x3.shape[1], x3.stride(0), w_all.stride(0), n_, dit_ops.EPI_STORE_F32) != 0
         tiled = self.head_dim == 32
         if tiled:
             nbytes = n_sets * H * ((L + 63) // 64) * 4096
@@ -509,8 +518,7 @@ class DiT(nn.Module):
             g1 = min(nb, g0 + G)
             n = (g1 - g0) * 2 * C
             wide = torch.empty((M, n), dtype=torch.float32, device=x3.device)
-            (dit_ops.gemm8 if g8(n) else dit_ops.gemm)(x3, w_all[g0 * 2 * C:g1 * 2 * C], None if bias_all is None else bias_all[g0 * 2 * C:g1 * 2 * C], wide,
-                                                       dit_ops.EPI_STORE_F32)
+            _gemm_f32_any_batch(x3, w_all[g0 * 2 * C:g1 * 2 * C], None if bias_all is None else bias_all[g0 * 2 * C:g1 * 2 * C], wide)
             if not tiled:
                 # head_dim 64: the strided flash attention reads row-major [k | v] rows of the operand type (one rounding of the fp32-class
                 # projection, as the tile image's); MultiHeadRMSNorm of k is the kernel's prologue (gamma_k)

@@ -153,7 +153,8 @@ def cast_pad_bf16(src, ld_dst=None, act=0, out=None):
 
 def gemm(a: torch.Tensor, w: torch.Tensor, bias, out: torch.Tensor, epilogue: int, gate: torch.Tensor = None,
               gate_ld: int = 0, rows_per_group: int = 0, n: int = None):
-    """out (M, >=N) <- epilogue(a (M,K) @ w (N,K)^T + bias).  a, w bf16 or fp16 (the same) with K % 64 == 0; a 16-bit `out` has their type."""
+    """out (M, >=N) <- epilogue(a (M,K) @ w (N,K)^T + bias).  a, w bf16 or fp16 (the same) with K % 32 == 0 (gvf_gemm refuses other K); a 16-bit
+    `out` has their type."""
     _lib.require_cuda(a, w, out)
     dt = _same_lp(a, w, out)
     assert a.stride(1) == 1 and w.stride(1) == 1

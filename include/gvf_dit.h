@@ -38,8 +38,14 @@ extern "C" {
                                     64 b + 32 + i); N % 64 == 0; bit-identical to the store epilogue followed by gvf_geglu */
 
 /* C = A W^T (+bias): A bf16 [M][lda] row-major, W bf16 [N][ldw] row-major (nn.Linear layout),
- * K a multiple of 64 (pad activations and weights), lda/ldw multiples of 8, bias f32 [N] or null.
- * gate f32: row g of `gate` (leading dimension gate_ld) applies to rows [g*rows_per_group, ...). */
+ * K a multiple of 32 (pad activations and weights; other K are refused), lda/ldw multiples of 8, bias f32 [N] or null.
+ * gate f32: row g of `gate` (leading dimension gate_ld) applies to rows [g*rows_per_group, ...).
+ * Row invariance: the four-wave kernel computes every output element as one fixed chain of 32-deep MFMA k-steps (ascending k, bias added
+ * after) whatever tile shape M selects, so a row's bits do not depend on the other rows of the call.  Across gvf_gemm's gvf_gemm8 threshold
+ * (below: eligible calls with at least one tile per CU) the rows also come out the same bits today -- gvf_gemm8 chains the same k-steps
+ * (measured for the store, fp32 store, GEGLU and residual epilogues: tests/test_gemm_conformance_gpu.py) -- but that is the two kernels'
+ * agreement, not a contract of the router: a caller whose numbers must not depend on the batch picks the kernel from N and K itself
+ * (DiT.prepare_conditions). */
 int gvf_gemm(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc,
              int M, int N, int K, int epilogue, const float* gate, int gate_ld, int rows_per_group, void* stream);
 int gvf_gemm_bf16(const void* A, int lda, const void* W, int ldw, const float* bias, void* C, int ldc,
