@@ -57,6 +57,10 @@ SIGNATURES = {
     "gvf_rast_backward": (_i, [ctypes.POINTER(GvfRastSettings), ctypes.POINTER(GvfRastFrame), _i, _i,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _vp, _vp, _vp, _vp, _sz,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gvf_rast_backward_batched_scratch_bytes": (_i, [_i, _i, ctypes.POINTER(_sz)]),
+    "gvf_rast_backward_batched": (_i, [ctypes.POINTER(GvfRastSettings), ctypes.POINTER(GvfRastFrame), _i,
+                                       ctypes.POINTER(GvfGaussianActivation), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                       _vp, _sz, _i64, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvf_gaussian_activate": (_i, [ctypes.POINTER(GvfGaussianActivation), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvf_rgb_to_u8": (_i, [_vp, _vp, _i64, _vp]),

@@ -4,7 +4,9 @@ Reference seam: renderers/gaussian_render.py:110-143 (settings) and :198-220 (op
 the reference imports the two classes from the external CUDA packages `diff_gaussian_rasterization`
 (mip-splatting fork) and `diff_gauss`; here they are backed by libgvf_hip.so (csrc/rast.hip).
 Differentiable: when an input requires grad, rasterize() runs through _RasterizeFn (forward keeps its
-workspace, backward calls gvf_rast_backward) -- upstream's _RasterizeGaussians autograd.Function.
+workspace, backward calls gvf_rast_backward) -- upstream's _RasterizeGaussians autograd.Function -- and
+rasterize_batched() through _RasterizeBatchedFn (gvf_rast_backward_batched: gradients of the raw GaussianModel
+parameters and of the per-frame deltas, F frames in one backward call).
 """
 import ctypes
 import os
@@ -243,7 +245,30 @@ def rasterize_batched(settings, frames, act, xyz_raw, features_dc, scaling_raw, 
 
     frames: list of GvfRastFrame (delta_index selects the (P,14) slice of delta[n_delta,P,14]).
     With sync=False no host sync happens; the caller must check `num_rendered.sum() <= max_rendered`.
+
+    Differentiable (color, alpha, depth w.r.t. xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta) when grad is enabled,
+    one of those requires grad and color_u8 is false: the call then runs through _RasterizeBatchedFn with a workspace of its own, kept for
+    the backward (mode MIP only).  Such a call always reads the instance count once (sync=False is ignored there: the backward needs a forward
+    that fitted its workspace) and grows and retries as the synchronous call does.
     """
+    diff = (torch.is_grad_enabled() and not color_u8 and
+            any(t is not None and t.requires_grad for t in (xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta)))
+    if diff:
+        _lib.require_cuda(xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta)
+        arr = (_lib.GvfRastFrame * len(frames))(*frames)
+        color, alpha, depth, radii, nr, cap = _RasterizeBatchedFn.apply(
+            settings, arr, act, bool(want_alpha_depth), bool(want_radii), max_rendered,
+            xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta)
+        return dict(color=color, alpha=alpha if want_alpha_depth else None, depth=depth if want_alpha_depth else None,
+                    radii=radii if want_radii else None, num_rendered=nr, max_rendered=int(cap))
+    return _rasterize_batched_impl(settings, frames, act, xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta,
+                                   want_alpha_depth, want_radii, max_rendered, sync, color_u8)
+
+
+def _rasterize_batched_impl(settings, frames, act, xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw,
+                            delta=None, want_alpha_depth=False, want_radii=False, max_rendered=None, sync=True, color_u8=False,
+                            private_workspace=False):
+    """private_workspace: the call gets its own workspace tensor (returned in the dict as in _rasterize_impl) and is synchronous."""
     _lib.require_cuda(xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta)
     dev = xyz_raw.device
     xyz_raw, features_dc = _f32c(xyz_raw, "xyz"), _f32c(features_dc, "features_dc")
@@ -258,7 +283,7 @@ def rasterize_batched(settings, frames, act, xyz_raw, features_dc, scaling_raw, 
         assert delta.shape[1] == P and delta.shape[2] == 14, "delta must be (n,P,14) [xyz3|scale3|rot4|rgb3|op1]"
         n_delta = delta.shape[0]
     F = len(frames)
-    arr = (_lib.GvfRastFrame * F)(*frames)
+    arr = frames if isinstance(frames, ctypes.Array) else (_lib.GvfRastFrame * F)(*frames)
     H, W = settings.image_height, settings.image_width
     if color_u8 and (want_alpha_depth or want_radii):
         raise _lib.GvfError("color_u8: the uint8 entry point has no alpha / depth / radii outputs")
@@ -271,7 +296,7 @@ def rasterize_batched(settings, frames, act, xyz_raw, features_dc, scaling_raw, 
     cap = max_rendered if max_rendered is not None else _CAP_HINT.get(key, max(4 * P * F, 1 << 16))
     while True:
         nbytes = workspace_bytes(P, F, H, W, cap)
-        ws = _workspace(dev, nbytes + 256)
+        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev) if private_workspace else _workspace(dev, nbytes + 256)
         base = (ws.data_ptr() + 255) // 256 * 256
         if color_u8:
             rc = _lib.lib().gvf_rast_forward_batched_u8(
@@ -285,9 +310,12 @@ def rasterize_batched(settings, frames, act, xyz_raw, features_dc, scaling_raw, 
                 ctypes.c_void_p(base), nbytes, cap, _lib.ptr(color), _lib.ptr(alpha), _lib.ptr(depth),
                 _lib.ptr(radii), _lib.ptr(nr), _lib.current_stream(dev))
         _lib.check(rc, "gvf_rast_forward_batched")
-        _LAST_CARVE[(dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))] = \
-            (ws, base, nbytes, P, F, H, W, cap)         # `ws`: the tensor itself, so that the address stays this workspace's
-        if not sync:
+        if private_workspace:
+            private = (ws, nbytes)
+        else:
+            _LAST_CARVE[(dev.index if dev.index is not None else torch.cuda.current_device(), int(torch.cuda.current_stream(dev).cuda_stream))] = \
+                (ws, base, nbytes, P, F, H, W, cap)     # `ws`: the tensor itself, so that the address stays this workspace's
+        if not sync and not private_workspace:
             break
         n = int(nr.to(torch.int64).bitwise_and(0xFFFFFFFF).sum().item())
         if n <= cap:
@@ -295,9 +323,87 @@ def rasterize_batched(settings, frames, act, xyz_raw, features_dc, scaling_raw, 
         if max_rendered is not None:
             raise _lib.GvfError(f"max_rendered={max_rendered} too small: {n} instances")
         cap = int(n * 1.25) + 1024
-    if sync:
+    if sync or private_workspace:
         _CAP_HINT[key] = cap
-    return dict(color=color, alpha=alpha, depth=depth, radii=radii, num_rendered=nr, max_rendered=cap)
+    out = dict(color=color, alpha=alpha, depth=depth, radii=radii, num_rendered=nr, max_rendered=cap)
+    if private_workspace:
+        out.update(workspace=private[0], workspace_bytes=private[1])
+    return out
+
+
+class _RasterizeBatchedFn(torch.autograd.Function):
+    """autograd wrapper of one batched, fused-activation call (gvf_rast_forward_batched -> gvf_rast_backward_batched).  Inputs that may
+    carry gradients: xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta -- only those with ctx.needs_input_grad are
+    computed (a null output is skipped by the library: detach_static).  Outputs: color (F,3,H,W), alpha, depth (F,H,W; empty placeholders
+    unless want_alpha_depth), radii (empty unless want_radii), num_rendered (F,), max_rendered (0-d)."""
+
+    @staticmethod
+    def forward(ctx, settings, frames, act, want_ad, want_radii, max_rendered, xyz_raw, features_dc, scaling_raw, rotation_raw,
+                opacity_raw, delta):
+        inputs = (xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta)
+        ctx.in_meta = tuple(None if t is None else (t.dtype, t.shape) for t in inputs)
+        # what backward hands to the C ABI must be what forward rendered: dense fp32 (see _RasterizeFn)
+        xyz_raw, features_dc, scaling_raw, rotation_raw = (_f32c(t, "input") for t in (xyz_raw, features_dc, scaling_raw, rotation_raw))
+        opacity_raw = _f32c(opacity_raw, "input").reshape(-1)
+        if delta is not None:
+            delta = _f32c(delta, "input")
+            if delta.dim() == 2:
+                delta = delta[None]
+        out = _rasterize_batched_impl(settings, frames, act, xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta,
+                                      want_ad, want_radii, max_rendered, True, False, private_workspace=True)
+        ctx.settings, ctx.frames, ctx.act, ctx.want_ad = settings, frames, act, want_ad
+        ctx.ws, ctx.ws_bytes, ctx.cap = out["workspace"], out["workspace_bytes"], out["max_rendered"]
+        ctx.has_delta = delta is not None
+        ctx.save_for_backward(xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw,
+                              delta if delta is not None else torch.empty(0))
+        dev = xyz_raw.device
+        empty = lambda dt=torch.float32: torch.empty((0,), dtype=dt, device=dev)
+        alpha = out["alpha"] if want_ad else empty()
+        depth = out["depth"] if want_ad else empty()
+        radii = out["radii"] if want_radii else empty(torch.int32)
+        cap = torch.tensor(out["max_rendered"], dtype=torch.int64)
+        ctx.mark_non_differentiable(radii, out["num_rendered"], cap)
+        return out["color"], alpha, depth, radii, out["num_rendered"], cap
+
+    @staticmethod
+    def backward(ctx, g_color, g_alpha, g_depth, _g_radii, _g_nr, _g_cap):
+        need = ctx.needs_input_grad[6:12]
+        if not any(need):
+            return (None,) * 12
+        xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta = ctx.saved_tensors
+        delta = delta if ctx.has_delta else None
+        dev = xyz_raw.device
+        P, M = xyz_raw.shape[0], features_dc.shape[1]
+        st = ctx.settings
+        F = len(ctx.frames)
+        H, W = st.image_height, st.image_width
+        n_delta = 0 if delta is None else delta.shape[0]
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_color = _f32c(g_color, "g") if g_color is not None else torch.zeros((F, 3, H, W), **f32)
+        g_alpha = _f32c(g_alpha, "g") if ctx.want_ad and g_alpha is not None else None
+        g_depth = _f32c(g_depth, "g") if ctx.want_ad and g_depth is not None else None
+        nb = ctypes.c_size_t(0)
+        _lib.check(_lib.lib().gvf_rast_backward_batched_scratch_bytes(P, F, ctypes.byref(nb)), "gvf_rast_backward_batched_scratch_bytes")
+        scratch = torch.empty(int(nb.value) + 16, dtype=torch.uint8, device=dev)
+        sbase = (scratch.data_ptr() + 15) // 16 * 16
+        outs = [torch.empty(shape, **f32) if n else None for n, shape in
+                zip(need, ((P, 3), (P, M, 3), (P, 3), (P, 4), (P,), (n_delta, P, 14)))]
+        base = (ctx.ws.data_ptr() + 255) // 256 * 256
+        rc = _lib.lib().gvf_rast_backward_batched(
+            ctypes.byref(st), ctx.frames, F, ctypes.byref(ctx.act), P, M, _lib.ptr(xyz_raw), _lib.ptr(features_dc),
+            _lib.ptr(scaling_raw), _lib.ptr(rotation_raw), _lib.ptr(opacity_raw), _lib.ptr(delta), n_delta,
+            ctypes.c_void_p(base), ctx.ws_bytes, ctx.cap, _lib.ptr(g_color), _lib.ptr(g_alpha), _lib.ptr(g_depth),
+            ctypes.c_void_p(sbase), int(nb.value), *[_lib.ptr(t) for t in outs], _lib.current_stream(dev))
+        _lib.check(rc, "gvf_rast_backward_batched")
+        grads = []
+        for g, meta in zip(outs, ctx.in_meta):
+            if g is not None:
+                dt, shape = meta
+                g = g.reshape(shape)
+                if g.dtype != dt:
+                    g = g.to(dt)
+            grads.append(g)
+        return (None,) * 6 + tuple(grads)
 
 
 _LAST_CARVE = {}     # (device index, stream handle) -> the workspace TENSOR + arguments of the last batched call there (sort_class_counts).

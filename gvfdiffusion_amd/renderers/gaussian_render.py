@@ -222,7 +222,10 @@ class GaussianRenderer:
         extrinsics / intrinsics / delta_index.  Returns edict(rgb (F,3,H,W) [, alpha, depth (F,H,W)], num_rendered (F,)).
         as_uint8: rgb comes back as uint8 = the reference's frame post-process (clamp(0,1) * 255 -> uint8, utils/inference_utils.py:280-286)
         done in the compositing kernel's epilogue -- bit-identical to rasterizer.frames_to_uint8(rgb), without the fp32 frames' trip through
-        HBM.  Falls back to that two-step form where the fused one does not apply (ssaa > 1, alpha / depth wanted, the dilation mode)."""
+        HBM.  Falls back to that two-step form where the fused one does not apply (ssaa > 1, alpha / depth wanted, the dilation mode).
+        Differentiable (mip mode) in delta_pc and in the Gaussian's _xyz, _features_dc (through get_features), _scaling, _rotation and
+        _opacity when grad is enabled and one of them requires it: the call then runs through rasterizer._RasterizeBatchedFn and its
+        backward through gvf_rast_backward_batched (the ssaa > 1 resize differentiates as a torch op).  as_uint8 frames carry no graph."""
         opts = self.rendering_options
         ssaa = int(opts["ssaa"])
         size = int(opts["resolution"]) * ssaa          # supersampled render, down-sampled below as render() does (gaussian_render.py:355-360)

@@ -6,7 +6,8 @@ truth image -> accelerator.backward), and the optimisation step of train_latent.
 clip_grad_norm_(params, 1.0) -> opt.step -> zero_grad) under accelerate's DDP, i.e. gradients averaged over the ranks.
 
 Here: one process per GPU, each rank renders ITS samples through gvf_rast_forward / gvf_rast_backward
-(gvfdiffusion_amd/rasterizer.py::_RasterizeFn), and the gradients of the trainable parameters are averaged with bucketed
+(gvfdiffusion_amd/rasterizer.py::_RasterizeFn; render_l1_loss) or all views at once through gvf_rast_forward_batched /
+gvf_rast_backward_batched (_RasterizeBatchedFn; render_l1_loss_frames), and the gradients of the trainable parameters are averaged with bucketed
 all-reduces on the default process group -- RCCL over xGMI on an MI355X node (backend "nccl"), gloo in the CPU tests.
 The HIP VAE / DiT kernels are inference kernels (no autograd through them); what trains here is whatever torch module
 produces the (T, P, 14) deltas -- `DeltaHead` is the decoder's last projection (model/autoencoder.py `to_outputs`) as a
@@ -43,6 +44,20 @@ def render_l1_loss(render_fn: Callable, gaussian, extrinsics: torch.Tensor, intr
         t = v if frame_of_view is None else int(frame_of_view[v])
         img = render_fn(gaussian, extrinsics[v], intrinsics, deltas[t])
         loss = loss + F.l1_loss(img, targets[v])
+    return loss / V
+
+
+def render_l1_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsics: torch.Tensor, deltas: torch.Tensor,
+                          targets: torch.Tensor, frame_of_view: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """render_l1_loss with the V views rendered in ONE renderer.render_frames call (GaussianRenderer: the batched fused-activation
+    rasteriser, differentiated by gvf_rast_backward_batched) instead of V single-frame renders: view v uses delta slice
+    frame_of_view[v] (default v).  Same loss: mean_v L1(frame_v, targets[v])."""
+    V = extrinsics.shape[0]
+    index = list(range(V)) if frame_of_view is None else [int(t) for t in frame_of_view]
+    imgs = renderer.render_frames(gaussian, extrinsics, intrinsics, delta_pc=deltas, delta_index=index)["rgb"]
+    loss = 0.0
+    for v in range(V):
+        loss = loss + F.l1_loss(imgs[v], targets[v])
     return loss / V
 
 

@@ -6,6 +6,7 @@
  *   renderers/gaussian_render.py:198-220  GaussianRasterizer(...)(means3D, ...) -> gvf_rast_forward()
  *   renderers/gaussian_render.py:154-160 + representations/gaussian/gaussian_model.py:84-114
  *        (get_*_with_delta, fused in front of the rasteriser)                  -> gvf_rast_forward_batched()
+ *   the autograd backward of both (train_vae.py:313-352)                     -> gvf_rast_backward(), gvf_rast_backward_batched()
  * The external CUDA packages behind that seam (diff_gaussian_rasterization [mip-splatting fork]
  * and diff_gauss [slothfulxtx fork]) are NOT in /root/reference (setup.sh:111,220-227); the two
  * `mode`s below select their published behaviours.
@@ -174,6 +175,32 @@ int gvf_rast_forward_batched_u8(const GvfRastSettings* settings_host, const GvfR
                                 void* workspace, size_t workspace_bytes, int64_t max_rendered,
                                 uint8_t* out_rgb_u8, uint32_t* out_num_rendered,
                                 void* stream);
+
+/* Backward of gvf_rast_forward_batched() (train_vae.py:313-352 renders B x n_cams views per step, each as render(static_gs, cam,
+ * delta_pc=pred_delta_b), and back-propagates an image loss into the deltas and the static Gaussians).  Same arguments as that forward call,
+ * whose workspace must be passed untouched since, with the same workspace_bytes / max_rendered: the backward reads the splat records, the
+ * sorted lists, the tile ranges, the camera blocks and the record layout (slot order or not, decided by the forward) from it.
+ * dL_dcolor[F][3][H][W] is required; dL_dalpha / dL_ddepth [F][H][W] may be null.  Mode GVF_RAST_MODE_MIP only (GVF_EINVAL otherwise).
+ * scratch: >= gvf_rast_backward_batched_scratch_bytes(P, F) bytes, 16-byte aligned (per-(frame, Gaussian) accumulators, zeroed here).
+ * Outputs, every one nullable (null: not computed -- detach_static), each non-null one fully written:
+ *   dL_dxyz_raw[P][3], dL_dfeatures_dc[P][M][3] (zero above the active degree), dL_dscaling_raw[P][3], dL_drotation_raw[P][4],
+ *   dL_dopacity_raw[P], dL_ddelta[n_delta][P][14] (exact zeros in slices no frame selects; a frame with delta_index -1 reaches only the
+ *   raw-parameter gradients).
+ * The activations differentiated are activate_vals' (aabb scale + offset; exp | softplus, then sqrt(s^2 + k^2); +1 on r and normalisation
+ * with the 1e-12 clamp; sigmoid; the rgb delta added to every SH row), recomputed with the forward's own device functions, then the
+ * single-frame chain rule per frame.  Deterministic up to the blend backward's fp32 atomics, as gvf_rast_backward. */
+int gvf_rast_backward_batched_scratch_bytes(int P, int F, size_t* bytes);
+int gvf_rast_backward_batched(const GvfRastSettings* settings_host, const GvfRastFrame* frames_host, int F,
+                              const GvfGaussianActivation* act_host, int P, int M,
+                              const float* xyz_raw, const float* features_dc, const float* scaling_raw,
+                              const float* rotation_raw, const float* opacity_raw,
+                              const float* delta, int n_delta,
+                              const void* workspace, size_t workspace_bytes, int64_t max_rendered,
+                              const float* dL_dcolor, const float* dL_dalpha, const float* dL_ddepth,
+                              void* scratch, size_t scratch_bytes,
+                              float* dL_dxyz_raw, float* dL_dfeatures_dc, float* dL_dscaling_raw,
+                              float* dL_drotation_raw, float* dL_dopacity_raw, float* dL_ddelta,
+                              void* stream);
 
 /* GaussianModel activations alone (get_*_with_delta), for callers that want the activated
  * tensors (and for parity tests of the fused path): writes means3D[P][3], scales[P][3],
