@@ -152,4 +152,5 @@ class SparseVAE:
         return self.to_representation(self.backbones["vae"].decode(latent))
 
     def training_losses(self, *a, **k):
-        raise NotImplementedError("static-VAE training losses (l1 / ssim / lpips, regularisers) are outside the hot path")
+        raise NotImplementedError("static-VAE training losses (l1 / ssim / lpips, regularisers) are outside the hot path; "
+                                  "the L1 + SSIM image loss is gvfdiffusion_amd.ops.image_loss.image_loss")

@@ -7,7 +7,7 @@ clip_grad_norm_(params, 1.0) -> opt.step -> zero_grad) under accelerate's DDP, i
 
 Here: one process per GPU, each rank renders ITS samples through gvf_rast_forward / gvf_rast_backward
 (gvfdiffusion_amd/rasterizer.py::_RasterizeFn; render_l1_loss) or all views at once through gvf_rast_forward_batched /
-gvf_rast_backward_batched (_RasterizeBatchedFn; render_l1_loss_frames), and the gradients of the trainable parameters are averaged with bucketed
+gvf_rast_backward_batched (_RasterizeBatchedFn; render_l1_loss_frames, render_loss_frames), and the gradients of the trainable parameters are averaged with bucketed
 all-reduces on the default process group -- RCCL over xGMI on an MI355X node (backend "nccl"), gloo in the CPU tests.
 The HIP VAE / DiT kernels are inference kernels (no autograd through them); what trains here is whatever torch module
 produces the (T, P, 14) deltas -- `DeltaHead` is the decoder's last projection (model/autoencoder.py `to_outputs`) as a
@@ -59,6 +59,21 @@ def render_l1_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsi
     for v in range(V):
         loss = loss + F.l1_loss(imgs[v], targets[v])
     return loss / V
+
+
+def render_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsics: torch.Tensor, deltas: torch.Tensor,
+                       targets: torch.Tensor, frame_of_view: Optional[Sequence[int]] = None, l1_weight: float = 1.0,
+                       ssim_weight: float = 0.2) -> torch.Tensor:
+    """The reference's render loss without its LPIPS term (train_vae.py:328-334):
+        l1_weight * L1(frames, targets) + ssim_weight * (1 - ssim(frames, targets))
+    over the stacked (V, 3, H, W) views, rendered in ONE renderer.render_frames call as in render_l1_loss_frames and scored by ONE
+    fused HIP loss (ops/image_loss.py: gvf_image_loss_forward / _backward).  For views of one size, the L1 over the stack equals
+    the mean of the per-view L1s of render_l1_loss_frames."""
+    from .ops.image_loss import image_loss
+    V = extrinsics.shape[0]
+    index = list(range(V)) if frame_of_view is None else [int(t) for t in frame_of_view]
+    imgs = renderer.render_frames(gaussian, extrinsics, intrinsics, delta_pc=deltas, delta_index=index)["rgb"]
+    return image_loss(imgs, targets, l1_weight=l1_weight, ssim_weight=ssim_weight)
 
 
 def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20) -> int:
