@@ -81,11 +81,7 @@ struct Cfg {
     // chunk swizzle that makes the per-lane 16-byte K fragment reads conflict-free
     // (a ds_read_b128 is served in lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32) over 64 banks: with 128-byte rows, lane = row, the
     // 16 rows of a group reach 16 distinct 16-byte slots for (key >> 1) & 7 -- key & 7 (rounds 1-3) put rows 12 and 20, 4 and 28, ... on one slot)
-#ifndef ATTN_SWZ64_OLD
     __device__ static __forceinline__ int swz(int key) { return KC == 4 ? ((key >> 2) & 3) : ((key >> 1) & 7); }
-#else
-    __device__ static __forceinline__ int swz(int key) { return KC == 4 ? ((key >> 2) & 3) : (key & 7); }
-#endif
 };
 
 // One staged 64-key tile for the 32 queries of a wave: S^T = K Q^T (both 32-key halves issued back to back),
@@ -467,9 +463,6 @@ constexpr int RES_THREADS = 64 * RES_WAVES;
 constexpr int RES_MAX_TILES = 8;
 constexpr int RES_ROUND = 4;                 // staging chunks per thread in flight per round
 
-#ifndef RES_NOMAX
-#define RES_NOMAX 1            // K/V-resident kernel: softmax without the running maximum (exact fallback per wave); 0 = always exact
-#endif
 #ifndef RES_SCHED
 #define RES_SCHED 6            // VALU instructions asked for behind every MFMA of a max-free tile step (0: scheduler's own order)
 #endif
@@ -484,8 +477,8 @@ __global__ __launch_bounds__(RES_THREADS) void attn_kvres_kernel(AttnParams p, i
     using C = Cfg<D>;
     typedef GvfLp<DT> LP;
     typedef typename LP::x8 x8;
-    // fp16: the max-free softmax with a per-query shift (tile_first_max), subtracted in front of the exponential (tile64_nomax)
-    constexpr bool NOMAX = RES_NOMAX != 0;
+    // softmax without the running maximum, with an exact fallback per wave.  fp16: with a per-query shift (tile_first_max), subtracted in
+    // front of the exponential (tile64_nomax)
     constexpr int CPT = KT * C::KC;                            // 16-byte chunks per K tile (= per V tile)
     extern __shared__ __attribute__((aligned(16))) unsigned char res_smem[];
     uint4* sK = reinterpret_cast<uint4*>(res_smem);                                            // [tiles][CPT]
@@ -547,7 +540,7 @@ __global__ __launch_bounds__(RES_THREADS) void attn_kvres_kernel(AttnParams p, i
                 if (C::KC == 8) ss += __shfl_xor(ss, 4, 64);
                 kw = rms_apply<D, DT>(kw, ss, gk8);
             }
-            if (NOMAX) kw = scale8<DT>(kw, p.scale_log2e);   // the scores then ARE the exp2 arguments (tile64_nomax)
+            kw = scale8<DT>(kw, p.scale_log2e);             // the scores then ARE the exp2 arguments (tile64_nomax)
             if (c < total) {
                 sK[(size_t)kt * CPT + kin * C::KC + (st_c ^ C::swz(kin))] = kw;
                 unsigned short* vt = sVT + (size_t)kt * res_vt_tile<D>();
@@ -571,7 +564,7 @@ __global__ __launch_bounds__(RES_THREADS) void attn_kvres_kernel(AttnParams p, i
     __syncthreads();
 
     // ---- every wave: its 32-query tiles over all key tiles, straight from LDS; RES_NQ tiles at a time (passes qt, qt + 1, ...)
-    constexpr int NQ = NOMAX ? RES_NQ : 1;
+    constexpr int NQ = RES_NQ;
     for (int qt = 0; qt < qt_per_wg; qt += NQ) {
         int qrow[NQ];
         bool qvalid[NQ];
@@ -608,49 +601,46 @@ __global__ __launch_bounds__(RES_THREADS) void attn_kvres_kernel(AttnParams p, i
         bool exact[NQ];
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
-            l_run[t] = 0.f; m_run[t] = -INFINITY; exact[t] = !NOMAX;
+            l_run[t] = 0.f; m_run[t] = -INFINITY; exact[t] = false;
 #pragma unroll
             for (int dt = 0; dt < C::ND; ++dt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) o_acc[t][dt][r] = 0.f;
         }
-        if (NOMAX) {
-            float cinit[NQ];                     // fp16: the shift of each query tile (its maximum over the first key tile); bf16: unused
+        float cinit[NQ];                     // fp16: the shift of each query tile (its maximum over the first key tile); bf16: unused
 #pragma unroll
-            for (int t = 0; t < NQ; ++t) cinit[t] = LP::kNeedsShift ? tile_first_max<D, DT>(sK, qf[t], l31, half) : 0.f;
-            for (int kt = 0; kt < n_tiles; ++kt) {
-                const uint4* kb = sK + (size_t)kt * CPT;
-                const unsigned short* vb = sVT + (size_t)kt * res_vt_tile<D>();
-                if (kt < last_full) tile64_nomax<D, false, NQ, DT>(kb, vb, kt * KT, Lk, qf, l31, half, o_acc, l_run, cinit);
-                else tile64_nomax<D, true, NQ, DT>(kb, vb, kt * KT, Lk, qf, l31, half, o_acc, l_run, cinit);
-            }
-            // every query's denominator must be finite and in range (2^-100 .. 2^100: no exp2 overflowed, not all of them vanished);
-            // otherwise the WAVE redoes that 32-query tile with the running-maximum softmax (keys are pre-scaled: scale 1)
+        for (int t = 0; t < NQ; ++t) cinit[t] = LP::kNeedsShift ? tile_first_max<D, DT>(sK, qf[t], l31, half) : 0.f;
+        for (int kt = 0; kt < n_tiles; ++kt) {
+            const uint4* kb = sK + (size_t)kt * CPT;
+            const unsigned short* vb = sVT + (size_t)kt * res_vt_tile<D>();
+            if (kt < last_full) tile64_nomax<D, false, NQ, DT>(kb, vb, kt * KT, Lk, qf, l31, half, o_acc, l_run, cinit);
+            else tile64_nomax<D, true, NQ, DT>(kb, vb, kt * KT, Lk, qf, l31, half, o_acc, l_run, cinit);
+        }
+        // every query's denominator must be finite and in range (2^-100 .. 2^100: no exp2 overflowed, not all of them vanished);
+        // otherwise the WAVE redoes that 32-query tile with the running-maximum softmax (keys are pre-scaled: scale 1)
 #pragma unroll
-            for (int t = 0; t < NQ; ++t) {
-                const float l_chk = l_run[t] + __shfl_xor(l_run[t], 32, 64);
-                // fp16: this kernel sums the UNROUNDED fp32 probabilities, so a probability beyond fp16's 65504 (inf as an MFMA operand) does
-                // not show in l by itself: bound l -- hence every probability -- by 2^15 (l >= 1 with the shift, see tile_first_max)
-                const bool bad = qvalid[t] && !(l_chk > (LP::kNeedsShift ? 0.015625f : 7.888609e-31f) && l_chk < (LP::kNeedsShift ? 32768.0f : 1.2676506e30f));
-                if (__any(bad)) {
-                    exact[t] = true;
-                    l_run[t] = 0.f;
+        for (int t = 0; t < NQ; ++t) {
+            const float l_chk = l_run[t] + __shfl_xor(l_run[t], 32, 64);
+            // fp16: this kernel sums the UNROUNDED fp32 probabilities, so a probability beyond fp16's 65504 (inf as an MFMA operand) does
+            // not show in l by itself: bound l -- hence every probability -- by 2^15 (l >= 1 with the shift, see tile_first_max)
+            const bool bad = qvalid[t] && !(l_chk > (LP::kNeedsShift ? 0.015625f : 7.888609e-31f) && l_chk < (LP::kNeedsShift ? 32768.0f : 1.2676506e30f));
+            if (__any(bad)) {
+                exact[t] = true;
+                l_run[t] = 0.f;
 #pragma unroll
-                    for (int dt = 0; dt < C::ND; ++dt)
+                for (int dt = 0; dt < C::ND; ++dt)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) o_acc[t][dt][r] = 0.f;
-                }
+                    for (int r = 0; r < 16; ++r) o_acc[t][dt][r] = 0.f;
             }
         }
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
             if (exact[t]) {
-                const float sc = NOMAX ? 1.0f : p.scale_log2e;
                 for (int kt = 0; kt < n_tiles; ++kt) {
                     const uint4* kb = sK + (size_t)kt * CPT;
                     const unsigned short* vb = sVT + (size_t)kt * res_vt_tile<D>();
-                    if (kt < last_full) tile64<D, false, DT>(kb, vb, kt * KT, Lk, sc, qf[t], l31, half, o_acc[t], m_run[t], l_run[t]);
-                    else tile64<D, true, DT>(kb, vb, kt * KT, Lk, sc, qf[t], l31, half, o_acc[t], m_run[t], l_run[t]);
+                    if (kt < last_full) tile64<D, false, DT>(kb, vb, kt * KT, Lk, 1.0f, qf[t], l31, half, o_acc[t], m_run[t], l_run[t]);
+                    else tile64<D, true, DT>(kb, vb, kt * KT, Lk, 1.0f, qf[t], l31, half, o_acc[t], m_run[t], l_run[t]);
                 }
             }
             const float l_tot = l_run[t] + __shfl_xor(l_run[t], 32, 64);

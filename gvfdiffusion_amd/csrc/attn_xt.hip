@@ -23,7 +23,7 @@
 // MFMAs of sub-tile Y}).  On gfx950 a SIMD overlaps MFMA and VALU work only when ONE wave interleaves them
 // (scripts/ubench/mfma_valu_overlap.hip), so the issue order of a phase is written out and fenced (sched_barrier).
 // The row sums of P are taken by the matrix pipe too (one v_mfma_f32_16x16x32 per 8 packed probabilities of a lane against a
-// 0 / 1 selector, see XT_SUM), i.e. the denominator sums the SAME bf16-rounded probabilities the numerator multiplies.  What bounds the loop is VALU issue: 32 v_exp_f32 (two issue slots each) + 16 v_cvt_pk +
+// 0 / 1 selector, see xt_phase), i.e. the denominator sums the SAME bf16-rounded probabilities the numerator multiplies.  What bounds the loop is VALU issue: 32 v_exp_f32 (two issue slots each) + 16 v_cvt_pk +
 // 16 MFMA issues per phase (profiles/r02_*attn_xt*: 104 issue quads per wave-phase, matrix pipe 43-53 % busy at the
 // 1.7 GHz the chip holds under this load).
 //
@@ -39,66 +39,6 @@
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 
-#ifndef XT_PIPELINE
-#define XT_PIPELINE 1        // 1: pin the MFMA / VALU interleave with sched_group_barrier
-#endif
-#ifndef XT_SUM_MFMA
-#define XT_SUM_MFMA 2        // 2: row sums of P by ONE v_mfma_f32_16x16x32 per 8 probabilities of a lane against a 0 / 1 selector (4 per tile and
-                             //    sub-tile, 16 cycles each); 1: by two v_mfma_f32_4x4x4 against ones (17 cycles each: rounds 2-3); 0: v_add
-#endif
-// Ablation switches for scripts/ubench/attn_xt_bench.hip (timing only: results are WRONG when any of them is set)
-#ifndef XT_ABL_NOEXP
-#define XT_ABL_NOEXP 0
-#endif
-#ifndef XT_ABL_NOQK
-#define XT_ABL_NOQK 0
-#endif
-#ifndef XT_ABL_NOPV
-#define XT_ABL_NOPV 0
-#endif
-#ifndef XT_ABL_NOSUM
-#define XT_ABL_NOSUM 0
-#endif
-#ifndef XT_ABL_NOCVT
-#define XT_ABL_NOCVT 0
-#endif
-#ifndef XT_ABL_EXPSRC
-#define XT_ABL_EXPSRC 0       // 1: the exponentials read lane constants instead of the score tile (no MFMA -> VALU dependency; scores kept alive)
-#endif
-#ifndef XT_UNROLL
-#define XT_UNROLL 1           // 1: the steady-state loop is unrolled over one period of the staging ring (TPS * NBUF tiles): ring slots become constants
-#endif
-#ifndef XT_ORDER
-#define XT_ORDER 0            // 0: every MFMA followed by 8-12 VALU instructions; 1: all VALU work of a phase first, then all its MFMAs
-#endif
-#ifndef XT_SKEW
-#define XT_SKEW 0             // > 0: waves in odd hardware wave slots sleep 64 * XT_SKEW clocks before the main loop
-#endif
-#ifndef XT_ABL_PCONST
-#define XT_ABL_PCONST 0       // 1: the PV / row-sum MFMAs read a loop-invariant operand instead of the probabilities (no VALU -> MFMA dependency)
-#endif
-#ifndef XT_ABL_NOSYNC
-#define XT_ABL_NOSYNC 0
-#endif
-#ifndef XT_ABL_NOLDS
-#define XT_ABL_NOLDS 0
-#endif
-#ifndef XT_ABL_LDSPAD
-#define XT_ABL_LDSPAD 0
-#endif
-#ifndef XT_SUM2
-#define XT_SUM2 1            // 1: two row-sum accumulators per sub-tile (no dependent pair of 4x4x4 MFMAs), 0: one (8 VGPRs less)
-#endif
-#ifndef XT_Q_LDS
-#define XT_Q_LDS 0            // 1: Q fragments parked in LDS (16 VGPRs less), re-read per phase
-#endif
-#ifndef XT_SETPRIO
-#define XT_SETPRIO 0
-#endif
-#ifndef XT_PERSIST
-#define XT_PERSIST 1          // 1: the grid is capped at the resident workgroup count and a workgroup walks several 256-query items, the next
-                              //    item's query rows and first two stages requested under the current item's epilogue; 0: one item per workgroup
-#endif
 #ifndef XT_TILES_PER_STAGE
 #define XT_TILES_PER_STAGE 2  // key tiles staged (and consumed) per workgroup barrier
 #endif
@@ -194,146 +134,71 @@ __device__ __forceinline__ typename GvfLp<DT>::x8 xt_ld_v(const uint4* sV, int g
     return __builtin_bit_cast(typename GvfLp<DT>::x8, sV[l31 * 8 + ((2 * g + half) ^ ((l31 >> 1) & 7))]);
 }
 
+// sQ and l4b are read by no code: without them the compiler allocates attn_xt_kernel's registers differently, so they stay until a change
+// that re-validates the kernel on the GPU removes them.
 // c0: initial value of the score accumulators.  bf16: zero (the compiler folds it into the MFMA's inline constant).  fp16: the splat of
 // minus the query's shift (see attn_xt_kernel) -- exp2 of a raw score would leave fp16's range.
 template <int DT, bool DO_QK, bool DO_SM, bool MASK, int PF, bool SHIFT = GvfLp<DT>::kNeedsShift>
 __device__ __forceinline__ void xt_phase(typename GvfLp<DT>::x8 (&kf)[2][2], typename GvfLp<DT>::x8 (&vf)[4], const uint4* __restrict__ sNext,
-                                         const typename GvfLp<DT>::x8 (&qf_in)[2], const uint4* __restrict__ sQ,
-                                         f32x16 (&s_out)[2], const f32x16 (&s_in)[2], f32x16& o_acc, float (&l_acc)[4], f32x4& l4, f32x4& l4b,
+                                         const typename GvfLp<DT>::x8 (&qf)[2], const uint4* __restrict__ sQ,
+                                         f32x16 (&s_out)[2], const f32x16 (&s_in)[2], f32x16& o_acc, f32x4& l4, f32x4& l4b,
                                          int l31, int half, int n_valid, const f32x16& c0) {
     typedef GvfLp<DT> LP;
     typedef typename LP::x8 x8;
-    typedef typename LP::x4 x4 __attribute__((unused));
     const f32x16 zero_ = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const f32x16 zero = SHIFT ? c0 : zero_;
     float pe[8];
     unsigned pw[4][4];
-    unsigned pconst[4] = {0x3c003c00u + (unsigned)l31, 0x3c003c01u, 0x3c003c02u, 0x3c003c03u};
-    if (XT_ABL_PCONST) asm volatile("" : "+v"(pconst[0]), "+v"(pconst[1]), "+v"(pconst[2]), "+v"(pconst[3]));
-    x8 qf[2];
-    if (XT_Q_LDS && DO_QK) { qf[0] = __builtin_bit_cast(x8, sQ[0]); qf[1] = __builtin_bit_cast(x8, sQ[64]); }
-    else { qf[0] = qf_in[0]; qf[1] = qf_in[1]; }
-#if XT_PIPELINE
-#define XT_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define XT_FENCE()
-#endif
 #define XT_E(g_)                                                                                            \
     if (DO_SM) {                                                                                            \
         _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                     \
-            if (XT_ABL_EXPSRC) { float t_ = 0.001f * (float)(l31 + e); asm volatile("v_exp_f32 %0, %1" : "=v"(pe[e]) : "v"(t_)); if (e == 0) asm volatile("" :: "v"(s_in[(g_) >> 1])); } \
-            else pe[e] = XT_ABL_NOEXP ? s_in[(g_) >> 1][8 * ((g_) & 1) + e] * 0.5f : __builtin_amdgcn_exp2f(s_in[(g_) >> 1][8 * ((g_) & 1) + e]); \
+            pe[e] = __builtin_amdgcn_exp2f(s_in[(g_) >> 1][8 * ((g_) & 1) + e]);                            \
             if (MASK) pe[e] = (16 * (g_) + 4 * half + (e & 3) + 8 * (e >> 2)) < n_valid ? pe[e] : 0.f;     \
         }                                                                                                   \
-        XT_FENCE();                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
     }
-#if XT_SUM_MFMA == 2
-    /* The lane's 8 probabilities (query l31, key half `half`) are a B operand of the 16x16x32 shape as they stand: there lane l is column l % 16,
+    /* Row sums by the matrix pipe: ONE v_mfma_f32_16x16x32 per 8 probabilities of a lane against a 0 / 1 selector (4 per tile and sub-tile,
+       16 cycles each; against two v_mfma_f32_4x4x4 of 17 cycles: 1-3 % per launch, profiles/HISTORY_r04.md item 2).
+       The lane's 8 probabilities (query l31, key half `half`) are a B operand of the 16x16x32 shape as they stand: there lane l is column l % 16,
        k-block l / 16 -- blocks 0 / 2 are the two key halves of query l % 16, blocks 1 / 3 those of query 16 + l % 16.  Against the selector
        A[i][k-block] = (i < 8) == (block even) rows 0-7 of the product sum query n, rows 8-15 query n + 16, both halves included: lane l's
        accumulator (column l % 16, rows 4 (l / 16) ..) holds the denominator of query (l % 16) + 16 (l / 32), fetched once in the epilogue. */
     const unsigned selw = ((((unsigned)l31 >> 3) ^ ((unsigned)l31 >> 4)) & 1u) ? 0u : LP::ONE2;
     const x8 sel = __builtin_bit_cast(x8, make_uint4(selw, selw, selw, selw));
-#define XT_SUM(g_)                                                                                          \
-    l4 = LP::mfma16(sel, __builtin_bit_cast(x8, make_uint4(pw[g_][0], pw[g_][1], pw[g_][2], pw[g_][3])), l4);
-#elif XT_SUM_MFMA
-#define XT_SUM(g_)                                                                                          \
-    {                                                                                                       \
-        const x4 ones = __builtin_bit_cast(x4, make_uint2(LP::ONE2, LP::ONE2));                             \
-        if (XT_ABL_PCONST) { asm volatile("" :: "v"(pw[g_][0]), "v"(pw[g_][1]), "v"(pw[g_][2]), "v"(pw[g_][3])); \
-            l4 = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pconst[0], pconst[1])), l4); l4b = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pconst[2], pconst[3])), l4b); } else { \
-        l4 = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pw[g_][0], pw[g_][1])), l4);                 \
-        if (XT_SUM2) l4b = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pw[g_][2], pw[g_][3])), l4b);  \
-        else l4 = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pw[g_][2], pw[g_][3])), l4); }          \
-    }
-#else
-#define XT_SUM(g_)                                                                                          \
-    if (!XT_ABL_NOSUM) { _Pragma("unroll") for (int e = 0; e < 8; ++e) l_acc[e & 3] += pe[e]; }
-#endif
-#define XT_C(g_)                                                                                            \
+#define XT_P(g_)                                                                                            \
     if (DO_SM) {                                                                                            \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) pw[g_][i] = XT_ABL_NOCVT ? __float_as_uint(pe[2 * i]) : LP::pack(pe[2 * i], pe[2 * i + 1]);    \
-    }
-#define XT_S(g_)                                                                                            \
-    if (DO_SM) {                                                                                            \
-        XT_SUM(g_)                                                                                          \
-        XT_FENCE();                                                                                         \
-    }
-#define XT_P(g_) XT_C(g_) XT_S(g_)
-    /* ORDER 2: units of {one big MFMA, 4 exponentials, one row-sum MFMA, 2 conversions}: every MFMA has VALU work of about its own length behind it */
-#define XT_EH(g_, h_)                                                                                       \
-    if (DO_SM) {                                                                                            \
-        _Pragma("unroll") for (int e = 4 * (h_); e < 4 * (h_) + 4; ++e) {                                   \
-            pe2[g_ & 1][e] = __builtin_amdgcn_exp2f(s_in[(g_) >> 1][8 * ((g_) & 1) + e]);                    \
-            if (MASK) pe2[g_ & 1][e] = (16 * (g_) + 4 * half + (e & 3) + 8 * (e >> 2)) < n_valid ? pe2[g_ & 1][e] : 0.f; \
-        }                                                                                                   \
-        XT_FENCE();                                                                                         \
-    }
-#define XT_CH(g_, h_)                                                                                       \
-    if (DO_SM) {                                                                                            \
-        _Pragma("unroll") for (int i = 2 * (h_); i < 2 * (h_) + 2; ++i) pw[g_][i] = LP::pack(pe2[g_ & 1][2 * i], pe2[g_ & 1][2 * i + 1]); \
-        XT_FENCE();                                                                                         \
-    }
-#define XT_SH(g_, h_)                                                                                       \
-    if (DO_SM) {                                                                                            \
-        const x4 ones = __builtin_bit_cast(x4, make_uint2(LP::ONE2, LP::ONE2));                             \
-        if ((h_) == 0) l4 = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pw[g_][0], pw[g_][1])), l4);  \
-        else l4b = LP::mfma4(ones, __builtin_bit_cast(x4, make_uint2(pw[g_][2], pw[g_][3])), l4b);          \
-        XT_FENCE();                                                                                         \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) pw[g_][i] = LP::pack(pe[2 * i], pe[2 * i + 1]);       \
+        l4 = LP::mfma16(sel, __builtin_bit_cast(x8, make_uint4(pw[g_][0], pw[g_][1], pw[g_][2], pw[g_][3])), l4); \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
     }
 #define XT_V(g_)                                                                                            \
-    if (DO_SM && !XT_ABL_NOPV) {                                                                            \
-        if (XT_SETPRIO) __builtin_amdgcn_s_setprio(1);                                                      \
-        o_acc = LP::mfma32(vf[g_], XT_ABL_PCONST ? __builtin_bit_cast(x8, make_uint4(pconst[0], pconst[1], pconst[2], pconst[3])) : __builtin_bit_cast(x8, make_uint4(pw[g_][0], pw[g_][1], pw[g_][2], pw[g_][3])), o_acc); \
-        if (XT_SETPRIO) __builtin_amdgcn_s_setprio(0);                                                      \
-        if (PF == 1 && !XT_ABL_NOLDS) vf[g_] = xt_ld_v<DT>(sNext, g_, l31, half);                              \
-        if (PF == 2 && !XT_ABL_NOLDS && ((g_) == 0 || (g_) == 3)) {   /* K fragments of the next tile: sub 0 behind V0 */ \
+    if (DO_SM) {                                                                                            \
+        o_acc = LP::mfma32(vf[g_], __builtin_bit_cast(x8, make_uint4(pw[g_][0], pw[g_][1], pw[g_][2], pw[g_][3])), o_acc); \
+        if (PF == 1) vf[g_] = xt_ld_v<DT>(sNext, g_, l31, half);                                            \
+        if (PF == 2 && ((g_) == 0 || (g_) == 3)) {   /* K fragments of the next tile: sub 0 behind V0 */     \
             kf[(g_) == 3][0] = xt_ld_k<DT>(sNext, (g_) == 3, 0, l31, half);   /* (Q1 is done), sub 1 behind V3 (end of phase) */ \
             kf[(g_) == 3][1] = xt_ld_k<DT>(sNext, (g_) == 3, 1, l31, half);                                   \
         }                                                                                                   \
-        XT_FENCE();                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
     }
 #define XT_Q(i_)                                                                                            \
-    if (DO_QK && !XT_ABL_NOQK) {                                                                            \
+    if (DO_QK) {                                                                                            \
         if (((i_) & 1) == 0) s_out[(i_) >> 1] = LP::mfma32(kf[(i_) >> 1][0], qf[0], zero);                  \
         else {                                                                                              \
             s_out[(i_) >> 1] = LP::mfma32(kf[(i_) >> 1][1], qf[1], s_out[(i_) >> 1]);                       \
         }                                                                                                   \
-        XT_FENCE();                                                                                         \
+        __builtin_amdgcn_sched_barrier(0);                                                                  \
     }
-    XT_FENCE();
-#if XT_ORDER == 2
-    float pe2[2][8];
-    XT_Q(0) XT_EH(0, 0) XT_CH(0, 0)
-    XT_Q(1) XT_EH(0, 1) XT_SH(0, 0) XT_CH(0, 1)
-    XT_V(0) XT_EH(1, 0) XT_SH(0, 1) XT_CH(1, 0)
-    XT_Q(2) XT_EH(1, 1) XT_SH(1, 0) XT_CH(1, 1)
-    XT_V(1) XT_EH(2, 0) XT_SH(1, 1) XT_CH(2, 0)
-    XT_Q(3) XT_EH(2, 1) XT_SH(2, 0) XT_CH(2, 1)
-    XT_V(2) XT_EH(3, 0) XT_SH(2, 1) XT_CH(3, 0)
-    XT_EH(3, 1) XT_SH(3, 0) XT_CH(3, 1)
-    XT_V(3) XT_SH(3, 1)
-#elif XT_ORDER == 1
-    XT_E(0) XT_C(0) XT_E(1) XT_C(1) XT_E(2) XT_C(2) XT_E(3) XT_C(3) XT_FENCE();
-    XT_Q(0) XT_Q(1) XT_Q(2) XT_Q(3) XT_V(0) XT_S(0) XT_V(1) XT_S(1) XT_V(2) XT_S(2) XT_V(3) XT_S(3)
-#else
+    __builtin_amdgcn_sched_barrier(0);
     XT_E(0) XT_Q(0) XT_P(0) XT_Q(1) XT_E(1) XT_V(0) XT_P(1) XT_Q(2) XT_E(2) XT_V(1) XT_P(2) XT_Q(3) XT_E(3) XT_V(2) XT_P(3) XT_V(3)
-#endif
-    if (PF == 1 && !DO_SM && !XT_ABL_NOLDS) {      // first phase of a workgroup: nothing to chase, load the V^T fragments now
+    if (PF == 1 && !DO_SM) {      // first phase of a workgroup: nothing to chase, load the V^T fragments now
 #pragma unroll
         for (int g = 0; g < 4; ++g) vf[g] = xt_ld_v<DT>(sNext, g, l31, half);
     }
 #undef XT_E
 #undef XT_P
-#undef XT_C
-#undef XT_S
-#undef XT_EH
-#undef XT_CH
-#undef XT_SH
 #undef XT_V
 #undef XT_Q
-#undef XT_SUM
-#undef XT_FENCE
 }
 
 // classic online softmax over one staged tile for ONE 32-query sub-tile (exact fallback; not pipelined)
@@ -446,7 +311,7 @@ __device__ __forceinline__ uint4 xt_mask_q(uint4 v4, bool valid) {
 // fits fp16 by itself, the kernel is the bf16 one with the other MFMA opcode (no 32 splat registers, no shift pass).  A broken
 // promise overflows to inf and lands in the same range guard -> exact fallback.
 //
-// PERSISTENT WORKGROUPS (round 5, XT_PERSIST).  What a 256-query workgroup does BEFORE its loop -- query rows from HBM, the first two
+// PERSISTENT WORKGROUPS (profiles/r05_attn_persist_ab.txt).  What a 256-query workgroup does BEFORE its loop -- query rows from HBM, the first two
 // stages, the two fill phases: 7-10 k cycles, ~4 k of them memory latency nothing hides at the start of a launch -- is 60 % of the loop time
 // of a spatial-attention workgroup (8 key tiles), 22 % of an image one (22), 8 % of a static one (64): profiles/r04_attn_xt_timing.txt.  The
 // DiT's launches have 768 such items for 512 resident workgroups, so the grid is capped at the resident count and a workgroup walks
@@ -461,7 +326,7 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
     typedef typename LP::x8 x8;
     // ring of XT_NBUF stages x XT_TPS tiles x (256 K chunks + 256 V^T chunks) + one chunk for the guard flag.  ONE LDS object on purpose:
     // with a second __shared__ variable hipcc drains the LDS-DMA queue (vmcnt(0)) in front of every ds_read.
-    __shared__ uint4 smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1 + XT_ABL_LDSPAD + (XT_Q_LDS ? XT_THREADS * 4 : 0) + XT_PF_CHUNKS];
+    __shared__ uint4 smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1 + XT_PF_CHUNKS];
     volatile int* s_bad = reinterpret_cast<volatile int*>(&smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS]);
 
     const int tid0 = threadIdx.x;
@@ -531,11 +396,11 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
     // the attention loop): decoded in the tail -- kernel arguments re-read, three integer divisions -- it cost 3.4 k cycles between the
     // guard's barriers and the first request (s_memtime stamps, profiles/r05_attn_xt_item_boundary.txt).  Its query rows are touched
     // (one dword per row into the landing zone nobody reads) so that the tail's real loads find them in L2.
-    const bool has_next = XT_PERSIST && item + item_step < item_end;
+    const bool has_next = item + item_step < item_end;
     XtItem nxt = cur;
     if (has_next) {
         nxt = xt_item(p, item + item_step);
-        uint4* pz = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1 + XT_ABL_LDSPAD + (XT_Q_LDS ? XT_THREADS * 4 : 0)];
+        uint4* pz = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1];
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             const int row = nxt.qb * XT_QB + wave * 64 + a * 32 + l31;
@@ -558,21 +423,14 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
 #pragma unroll
         for (int st = 0; st < 2; ++st) qf[a][st] = __builtin_bit_cast(x8, qraw[a][st]);
     }
-    // XT_Q_LDS: the wave's four Q fragments live in its own 4 KiB of LDS ([sub-tile][k-step][lane]); no barrier needed (wave-private)
-    uint4* sQw = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1 + XT_ABL_LDSPAD] + wave * 256 + lane;
-    if (XT_Q_LDS) {
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int st = 0; st < 2; ++st) sQw[(a * 2 + st) * 64] = __builtin_bit_cast(uint4, qf[a][st]);
-        __builtin_amdgcn_wave_barrier();
-    }
+
+    uint4* sQw = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1] + wave * 256 + lane;      // xt_phase's unused sQ (see there)
 
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x16 oA = zero, oB = zero;
-    float lA4[4] = {0.f, 0.f, 0.f, 0.f}, lB4[4] = {0.f, 0.f, 0.f, 0.f};
     float lA = 0.f, lB = 0.f;
-    f32x4 l4A = {0.f, 0.f, 0.f, 0.f}, l4B = {0.f, 0.f, 0.f, 0.f}, l4Ab = {0.f, 0.f, 0.f, 0.f}, l4Bb = {0.f, 0.f, 0.f, 0.f};
+    f32x4 l4A = {0.f, 0.f, 0.f, 0.f}, l4B = {0.f, 0.f, 0.f, 0.f};
+    f32x4 l4Ab = {0.f, 0.f, 0.f, 0.f}, l4Bb = {0.f, 0.f, 0.f, 0.f};     // xt_phase's unused l4b (see there)
     bool bad = force_safe != 0;
     const uint4* const kbase = cur.kbase;
     const uint4* const vbase = cur.vbase;
@@ -581,9 +439,6 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
         f32x16 sA[2], sB[2];
         f32x16 cA = zero, cB = zero;        // fp16: -shift of the lane's query in sub-tile A / B (see xt_take_shift); bf16: unused
         x8 kf[2][2], vf[4];
-        if (XT_ABL_NOLDS) {       // timing experiment: fragments as opaque register values, no LDS traffic
-            for (int i = 0; i < 4; ++i) { asm volatile("" : "=v"(kf[i >> 1][i & 1])); asm volatile("" : "=v"(vf[i])); }
-        }
         // Tile t is consumed in iteration t: phase 1 = QK^T of sub-tile A on K(t) | softmax + PV of sub-tile B on V(t-1),
         // phase 2 = QK^T of B on K(t) | softmax + PV of A on V(t).  Phase 1 refills the V^T fragments with V(t), phase 2
         // the K fragments with K(t+1): tile t+1 must have landed when iteration t starts, so tiles are staged TWO ahead.
@@ -600,30 +455,24 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
             // warm the NEXT launch's weights: one dword per 128-byte line, LDS-DMA into a landing zone nobody reads (no register, no wait of
             // its own: the loads ride with the stage requests and are drained by the loop's barriers).  The lines end up in the Infinity
             // Cache (and this XCD's L2), where the row-block launch that follows finds them instead of going to HBM.
-            uint4* pz = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1 + XT_ABL_LDSPAD + (XT_Q_LDS ? XT_THREADS * 4 : 0)];
+            uint4* pz = &smem[XT_NBUF * XT_TPS * XT_TILE_CHUNKS + 1];
             for (int it = 0; it < p.pf_iters; ++it) {
                 const long long line = ((long long)it * gridDim.x + blockIdx.x) * 64 + lane;
                 if (line < p.pf_lines)
                     __builtin_amdgcn_global_load_lds(p.pf + line * 128, (__attribute__((address_space(3))) void*)pz, 4, 0, 0);
             }
         }
-        if (!XT_ABL_NOLDS) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) kf[i >> 1][i & 1] = xt_ld_k<DT>(XT_K(0), i >> 1, i & 1, l31, half);
-        }
-        xt_phase<DT, true, false, false, 1, SHIFT>(kf, vf, XT_V(0), qf[0], sQw, sA, sB, oB, lB4, l4B, l4Bb, l31, half, XT_KT, cA);
+        for (int i = 0; i < 4; ++i) kf[i >> 1][i & 1] = xt_ld_k<DT>(XT_K(0), i >> 1, i & 1, l31, half);
+        xt_phase<DT, true, false, false, 1, SHIFT>(kf, vf, XT_V(0), qf[0], sQw, sA, sB, oB, l4B, l4Bb, l31, half, XT_KT, cA);
         if (SHIFT) xt_take_shift<DT>(sA, cA);
-#if XT_SKEW
-        if (__builtin_amdgcn_s_getreg(((4 - 1) << 11) | 4) & 1) __builtin_amdgcn_s_sleep(XT_SKEW);      // HW_ID.WAVE_ID
-#endif
         if (T > 1) {
-            xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_K(1), qf[1], sQw + 128, sB, sA, oA, lA4, l4A, l4Ab, l31, half, XT_KT, cB);
+            xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_K(1), qf[1], sQw + 128, sB, sA, oA, l4A, l4Ab, l31, half, XT_KT, cB);
             if (SHIFT) xt_take_shift<DT>(sB, cB);
             // steady state, iterations t = 1 .. T-2.  Entering stage s = t / TPS: one barrier -- stage s+1 has landed
             // (iteration t may prefetch K(t+1) from it) and every wave is done with stage s-1, whose ring slot takes the
             // DMA of stage s+2.
             int t = 1;
-#if XT_UNROLL
             // whole periods of the ring: tile t + j sits at ring position (1 + j) % PER whenever (t - 1) % PER == 0 -- every LDS address of the
             // body is the lane's base plus a constant, the stage test a constant
             constexpr int PER = XT_TPS * XT_NBUF;
@@ -640,7 +489,7 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
 #endif
 #pragma unroll
                 for (int j = 0; j < PER; ++j) {
-                    if (!XT_ABL_NOSYNC && (1 + j) % XT_TPS == 0) {
+                    if ((1 + j) % XT_TPS == 0) {
 #ifdef XT_TIMING
                         const long long b0 = (long long)__builtin_amdgcn_s_memtime();
                         __syncthreads();
@@ -659,8 +508,8 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
                             }
                         }
                     }
-                    xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_RING(1 + j) + 256, qf[0], sQw, sA, sB, oB, lB4, l4B, l4Bb, l31, half, XT_KT, cA);
-                    xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_RING(2 + j), qf[1], sQw + 128, sB, sA, oA, lA4, l4A, l4Ab, l31, half, XT_KT, cB);
+                    xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_RING(1 + j) + 256, qf[0], sQw, sA, sB, oB, l4B, l4Bb, l31, half, XT_KT, cA);
+                    xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_RING(2 + j), qf[1], sQw + 128, sB, sA, oA, l4A, l4Ab, l31, half, XT_KT, cB);
                 }
             }
 #undef XT_RING
@@ -671,49 +520,36 @@ __global__ __launch_bounds__(XT_THREADS, XT_WAVES_PER_SIMD) void attn_xt_kernel(
                 d[0] = xt_loop1 - xt_t0; d[1] = xt_bar; d[2] = xt_tiles; d[3] = xt_loop0 - xt_k0;
             }
 #endif
-#endif
             for (; t + 1 < T; ++t) {
-                if (!XT_ABL_NOSYNC && t % XT_TPS == 0) {
+                if (t % XT_TPS == 0) {
                     __syncthreads();
                     const int s2 = t / XT_TPS + (XT_NBUF - 1);
                     if (s2 < n_stages) { XT_STAGE(s2) }
                 }
-                xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_V(t), qf[0], sQw, sA, sB, oB, lB4, l4B, l4Bb, l31, half, XT_KT, cA);
-                xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_K(t + 1), qf[1], sQw + 128, sB, sA, oA, lA4, l4A, l4Ab, l31, half, XT_KT, cB);
+                xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_V(t), qf[0], sQw, sA, sB, oB, l4B, l4Bb, l31, half, XT_KT, cA);
+                xt_phase<DT, true, true, false, 2, SHIFT>(kf, vf, XT_K(t + 1), qf[1], sQw + 128, sB, sA, oA, l4A, l4Ab, l31, half, XT_KT, cB);
             }
             if ((T - 1) % XT_TPS == 0) __syncthreads();      // the last tile opens a stage: it must have landed
-            xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_V(T - 1), qf[0], sQw, sA, sB, oB, lB4, l4B, l4Bb, l31, half, XT_KT, cA);
+            xt_phase<DT, true, true, false, 1, SHIFT>(kf, vf, XT_V(T - 1), qf[0], sQw, sA, sB, oB, l4B, l4Bb, l31, half, XT_KT, cA);
         }
-        xt_phase<DT, true, true, true, 0, SHIFT>(kf, vf, XT_K(0), qf[1], sQw + 128, sB, sA, oA, lA4, l4A, l4Ab, l31, half, last_valid, cB);
+        xt_phase<DT, true, true, true, 0, SHIFT>(kf, vf, XT_K(0), qf[1], sQw + 128, sB, sA, oA, l4A, l4Ab, l31, half, last_valid, cB);
         if (SHIFT && T == 1) xt_take_shift<DT>(sB, cB);      // a single key tile: sub-tile B's first scores come out of this phase
-        xt_phase<DT, false, true, true, 0, SHIFT>(kf, vf, XT_K(0), qf[1], sQw, sA, sB, oB, lB4, l4B, l4Bb, l31, half, last_valid, cB);
-#if XT_SUM_MFMA == 2
+        xt_phase<DT, false, true, true, 0, SHIFT>(kf, vf, XT_K(0), qf[1], sQw, sA, sB, oB, l4B, l4Bb, l31, half, last_valid, cB);
         lA = __shfl(l4A[0], (l31 & 15) + 32 * (l31 >> 4), 64);      // both key halves are in already
         lB = __shfl(l4B[0], (l31 & 15) + 32 * (l31 >> 4), 64);
-#else
-#if XT_SUM_MFMA
-        lA = l4A[0] + l4Ab[0]; lB = l4B[0] + l4Bb[0];
-#else
-        lA = (lA4[0] + lA4[1]) + (lA4[2] + lA4[3]);
-        lB = (lB4[0] + lB4[1]) + (lB4[2] + lB4[3]);
-#endif
-        lA += __shfl_xor(lA, 32, 64);
-        lB += __shfl_xor(lB, 32, 64);
-#endif
         // range guard.  fp16: with the shift the denominator is >= 1 unless a single, partly padded key tile
         // pushed every probability under 2^-12 (the padding's zero scores took part in the shift)
         // fp16 without the shift (bounded scores): every probability is >= 2^-14, so is the sum; below that the promise was broken
         const float l_min = SHIFT ? 0.015625f : (LP::kNeedsShift ? 3.0517578125e-05f : 7.8886e-31f);
-        // upper bound: with XT_SUM_MFMA the sum is taken over the ROUNDED probabilities, so an fp16 overflow shows up as l = inf; a build that
-        // sums the fp32 values (XT_SUM_MFMA=0) must bound l below fp16's largest number itself (as attn.hip's kvres kernel does)
-        const float l_max = (!XT_SUM_MFMA && LP::kNeedsShift) ? 32768.0f : 1.2676e30f;
+        // upper bound: the sum is taken over the ROUNDED probabilities, so an fp16 overflow shows up as l = inf (a sum of the fp32 values would
+        // have to bound l below fp16's largest number itself, as attn.hip's kvres kernel does)
+        const float l_max = 1.2676e30f;
         // compared as BIT PATTERNS: this file is built with -fno-honor-nans, under which a float comparison may be inverted; as unsigned integers
         // positive floats order like their values, NaNs of either sign and every negative number fall outside [l_min, l_max) by themselves
         // (a NaN is what the selector form of the row sums makes of an infinity: 0 * inf)
         const unsigned u_min = __float_as_uint(l_min), u_span = __float_as_uint(l_max) - __float_as_uint(l_min);
         const bool okA = (__float_as_uint(lA) - u_min - 1u) < (u_span - 1u), okB = (__float_as_uint(lB) - u_min - 1u) < (u_span - 1u);
         bad = !(okA && okB);
-        if (XT_ABL_NOEXP || XT_ABL_NOQK || XT_ABL_NOPV || XT_ABL_NOSUM || XT_ABL_NOSYNC || XT_ABL_NOLDS) bad = false;   // timing experiments
     }
     XT_STAMP(0, xt_item_no == 0)
     XT_STAMP(7, xt_item_no == 1)
@@ -1091,11 +927,9 @@ extern "C" int gvf_attn_tiled_fwd_pf(int dtype, const void* q, const void* k_til
     long long blocks = (long long)p.q_blocks * H * n_inner * n_outer;
     if (blocks > 0x7fffffffLL) return GVF_EINVAL;
     p.n_items = (int)blocks;
-    if (XT_PERSIST) {                 // no more workgroups than are resident at once: each walks its share of the items (see attn_xt_kernel)
-        const long long res = (long long)xt_resident_workgroups();
-        static const bool off = [] { const char* e = getenv("GVF_ATTN_PERSIST"); return e && e[0] == '0'; }();      // measurement switch
-        if (!off && blocks > res) blocks = res;
-    }
+    // no more workgroups than are resident at once: each walks its share of the items (see attn_xt_kernel)
+    const long long res = (long long)xt_resident_workgroups();
+    if (blocks > res) blocks = res;
     if (p.pf != nullptr) p.pf_iters = (int)((p.pf_lines + blocks * 64 - 1) / (blocks * 64));
     (void)hipGetLastError();
     const int force_safe = force_exact & GVF_ATTN_FORCE_EXACT;

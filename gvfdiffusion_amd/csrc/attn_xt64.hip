@@ -26,9 +26,6 @@
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 
-#ifndef X64_ORDER
-#define X64_ORDER 0            // issue order of a phase (see x64_phase)
-#endif
 #ifndef X64_PASSES
 #define X64_PASSES 8           // 256-query passes per workgroup = per copy of the key set into LDS
 #endif
@@ -99,7 +96,7 @@ __device__ __forceinline__ void x64_phase(typename GvfLp<DT>::x8 (&kf)[2][4], ty
     typedef typename LP::x8 x8;
     float pe[8];
     unsigned pw[4][4];
-    // row sums: the lane's 8 probabilities as the B operand of a 16x16x32 MFMA against a 0 / 1 selector (attn_xt.hip, XT_SUM_MFMA = 2)
+    // row sums: the lane's 8 probabilities as the B operand of a 16x16x32 MFMA against a 0 / 1 selector (as in attn_xt.hip)
     const unsigned selw = ((((unsigned)l31 >> 3) ^ ((unsigned)l31 >> 4)) & 1u) ? 0u : LP::ONE2;
     const x8 sel = __builtin_bit_cast(x8, make_uint4(selw, selw, selw, selw));
 #define X_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -135,25 +132,11 @@ __device__ __forceinline__ void x64_phase(typename GvfLp<DT>::x8 (&kf)[2][4], ty
         X_FENCE();                                                                                          \
     }
     X_FENCE();
-#if X64_ORDER == 1
-    // coarse (attn_xt's shape): a block of 8 exponentials, then MFMAs
-    X_EH(0, 0) X_EH(0, 1) X_Q(0) X_Q(1) X_CH(0, 0) X_CH(0, 1) X_S(0) X_Q(2) X_Q(3)
-    X_EH(1, 0) X_EH(1, 1) X_V(0, 0) X_V(0, 1) X_CH(1, 0) X_CH(1, 1) X_S(1) X_Q(4) X_Q(5)
-    X_EH(2, 0) X_EH(2, 1) X_V(1, 0) X_V(1, 1) X_CH(2, 0) X_CH(2, 1) X_S(2) X_Q(6) X_Q(7)
-    X_EH(3, 0) X_EH(3, 1) X_V(2, 0) X_V(2, 1) X_CH(3, 0) X_CH(3, 1) X_S(3) X_V(3, 0) X_V(3, 1)
-#elif X64_ORDER == 2
-    // the two score chains interleaved (no MFMA waits on the one before it), half a chunk of vector work behind every MFMA
-    X_Q(0) X_EH(0, 0) X_Q(4) X_EH(0, 1) X_Q(1) X_CH(0, 0) X_CH(0, 1) X_S(0) X_Q(5) X_EH(1, 0)
-    X_V(0, 0) X_EH(1, 1) X_V(0, 1) X_CH(1, 0) X_CH(1, 1) X_S(1) X_Q(2) X_EH(2, 0)
-    X_V(1, 0) X_EH(2, 1) X_V(1, 1) X_CH(2, 0) X_CH(2, 1) X_S(2) X_Q(6) X_EH(3, 0)
-    X_V(2, 0) X_EH(3, 1) X_V(2, 1) X_CH(3, 0) X_CH(3, 1) X_S(3) X_Q(3) X_V(3, 0) X_Q(7) X_V(3, 1)
-#else
     // half a chunk of vector work (4 exponentials, or 4 conversions + the row-sum MFMA) behind every big MFMA
     X_Q(0) X_EH(0, 0) X_Q(1) X_EH(0, 1) X_Q(2) X_CH(0, 0) X_CH(0, 1) X_S(0) X_Q(3) X_EH(1, 0)
     X_V(0, 0) X_EH(1, 1) X_V(0, 1) X_CH(1, 0) X_CH(1, 1) X_S(1) X_Q(4) X_EH(2, 0)
     X_V(1, 0) X_EH(2, 1) X_V(1, 1) X_CH(2, 0) X_CH(2, 1) X_S(2) X_Q(5) X_EH(3, 0)
     X_V(2, 0) X_EH(3, 1) X_V(2, 1) X_CH(3, 0) X_CH(3, 1) X_S(3) X_Q(6) X_V(3, 0) X_Q(7) X_V(3, 1)
-#endif
     if (PF == 1 && !DO_SM) {           // first phase of a pass: nothing to chase, load the V^T fragments now
 #pragma unroll
         for (int g = 0; g < 4; ++g) { vf[g][0] = x64_ld_v<DT>(sNext, g, 0, l31, half); vf[g][1] = x64_ld_v<DT>(sNext, g, 1, l31, half); }
@@ -295,9 +278,7 @@ __global__ __launch_bounds__(X64_THREADS) void attn_xt64_kernel(X64Params p, int
 #pragma unroll
             for (int st = 0; st < 4; ++st) qf[a][st] = __builtin_bit_cast(x8, make_uint4(qn[a][st].x & m, qn[a][st].y & m, qn[a][st].z & m, qn[a][st].w & m));
         }
-#if !defined(X64_ABL_NOQ)
         if (pass + 1 < X64_PASSES && q_base + (pass + 1) * X64_THREADS < p.Lq) load_q(pass + 1);
-#endif
     };
     take_q(0);
     for (int pass = 0; pass < X64_PASSES; ++pass) {
@@ -424,18 +405,12 @@ __global__ __launch_bounds__(X64_THREADS) void attn_xt64_kernel(X64Params p, int
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int row = k * 8 + (lane >> 3), c = lane & 7;
-#if !defined(X64_ABL_NOSTORE) && !defined(X64_PLAIN_STORE)
                 // streaming stores: the 1.5 KiB rows of a 43 k-Gaussian chunk (1.6 GB per launch) are read once, by the GEMM behind this launch
                 if (row0 + row < p.Lq) {
                     unsigned* dst = reinterpret_cast<unsigned*>(op + (long long)(row0 + row) * p.o_sl + 8 * c);
                     __builtin_nontemporal_store(ov[k].x, dst); __builtin_nontemporal_store(ov[k].y, dst + 1);
                     __builtin_nontemporal_store(ov[k].z, dst + 2); __builtin_nontemporal_store(ov[k].w, dst + 3);
                 }
-#elif !defined(X64_ABL_NOSTORE)
-                if (row0 + row < p.Lq) *reinterpret_cast<uint4*>(op + (long long)(row0 + row) * p.o_sl + 8 * c) = ov[k];
-#else
-                if (row0 + row < p.Lq && ov[k].x == 0x12345678u) *reinterpret_cast<uint4*>(op + (long long)(row0 + row) * p.o_sl + 8 * c) = ov[k];
-#endif
             }
         }
         X64_STAMP(9 + 8 * pass);

@@ -21,13 +21,8 @@ __device__ __forceinline__ unsigned short f2bf(float f) {
 }
 
 // Sum over the 64 lanes, every lane gets it -- on the DPP / permlane data paths only (quad_perm, row mirrors, v_permlane16_swap,
-// v_permlane32_swap), nothing through the LDS unit.  #ifdef GVF_WAVE_SUM_BPERMUTE: the round-1 form (six ds_bpermute butterflies).
+// v_permlane32_swap), nothing through the LDS unit.
 __device__ __forceinline__ float wave_sum(float v) {
-#ifdef GVF_WAVE_SUM_BPERMUTE
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-#else
 #define GVF_DPP(x_, ctrl_) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x_), ctrl_, 0xF, 0xF, false))
     v += GVF_DPP(v, 0xB1);      // quad_perm [1,0,3,2]: lane ^ 1
     v += GVF_DPP(v, 0x4E);      // quad_perm [2,3,0,1]: lane ^ 2
@@ -42,7 +37,6 @@ __device__ __forceinline__ float wave_sum(float v) {
     const auto r32 = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);
     const unsigned b0 = r32[0], b1 = r32[1];
     return __uint_as_float(b0) + __uint_as_float(b1);
-#endif
 }
 
 // VPL = float4 loads per lane: C = 64 * 4 * VPL

@@ -58,47 +58,14 @@ constexpr int NSLAB = 1;
 #endif
 constexpr int PRE_FB = GVF_PRE_FB;   // frames per preprocess workgroup: the frame-invariant inputs (xyz, scale, rotation, opacity,
                             // SH: 164 of the 220 input bytes per Gaussian at degree 2) come from HBM once per PRE_FB frames
-// Workgroup -> (Gaussian block, frame group) of preprocess_kernel.  1: XCD-aware (round 5 experiment): workgroup n of the 1-D grid runs on XCD n % 8
-// (round-robin dispatch); the FY frame groups of one Gaussian block are consecutive workgroups OF ONE XCD, so the block's frame-invariant
-// 164 B per Gaussian cross the fabric once and are L2 hits for the other FY - 1 groups.  0 (default): round 1-4's (blocks, frame groups) 2-D grid,
-// in which a frame group walks all 43 MB of static inputs before the next one starts.  Measured: 0.363-0.366 ms with the XCD order against
-// 0.358 ms without (profiles/r05_preprocess_variants_ab.txt) -- the launch does not wait for those bytes.
-#ifndef GVF_PRE_XCD
-#define GVF_PRE_XCD 0
-#endif
-// 1: both preprocess launches store their splat records quad-transposed, whole 64-byte lines per instruction (see there).  The fused launch
-// took it once its bin records left as whole lines too: 283 -> 266 us per launch, 70 -> 83 registers, still 5 waves per SIMD (the SH staging
-// binds); before that its gain was inside the noise (0.377 -> 0.368 ms, round 5).  0: three 16-byte stores per lane in both.
-#ifndef GVF_PRE_REC_QUAD
-#define GVF_PRE_REC_QUAD 1
-#endif
-// 1: the delta row of frame ff + 1 is requested before frame ff's arithmetic (experiment; no gain: same file)
-#ifndef GVF_PRE_PREFETCH
-#define GVF_PRE_PREFETCH 0
-#endif
-// 1: preprocess_kernel<false> stages its workgroup's 256 delta rows (56 B each, one contiguous 14 KiB span per frame) through LDS with coalesced
-// 16-byte loads; the span of frame ff + 1 is loaded into registers before frame ff's arithmetic and written to LDS after it (one LDS buffer:
-// the rows move to registers first).  Experiment, not built by default and covered by no test there: the 14 KiB of LDS leave 3 workgroups per
-// CU instead of 5 at SH degree 2 (127 registers), and the launch is SLOWER, 283 -> 306 us (266 -> 296 us with the quad-transposed records;
-// profiles/r07_preprocess_forms_ab.txt).  The per-lane row gathers are not what holds the launch back once the stores are whole lines.
-#ifndef GVF_PRE_DELTA_LDS
-#define GVF_PRE_DELTA_LDS 0
-#endif
-// Bucket binning of the calls without shared activation (the fused launch preprocess_kernel<false>): where the bin records go and how the
-// count / scatter passes walk them.
-//   0: records stored at the Gaussian's Morton slot (a 16-byte store to an effectively random place in the frame's 4 MB per lane), the bin
-//      passes read them by slot as one stream (round 1-6 form).
-//   1: records stored at the Gaussian's own index (coalesced lines); bin_kernel gathers them by Morton order, each XCD taking whole frames so
-//      that a frame's 4 MB of records is gathered from its own L2.
-//   2: as 1, but the count pass is bin_index_kernel<false>: it walks the records in index order against a whole-frame LDS tile table.
-//   3: both passes in index order (bin_index_kernel), no Morton order for these calls.
-// Measured at the bench shape (one box, per launch): 0: preprocess 355 us, count 44, scatter 71, Morton launches 52; 1: preprocess 287,
-// count 67, scatter 95; 3: preprocess 286, count 32, scatter 222 (a workgroup's run per tile shrinks to ~11 keys); 2 takes the cheaper pass
-// of each (profiles/r07_bin_layout_ab.txt).  The default build runs 2 (and 0's layout on the shared-activation path); 1, 3 and with them
-// bin_index_kernel<true> are A/B switches, built only by `_build --variant` and covered by no test there.
-#ifndef GVF_BIN_ALGO
-#define GVF_BIN_ALGO 2
-#endif
+// preprocess_kernel runs on a (Gaussian blocks, frame groups) grid.  Measured and not adopted (profiles/r05_preprocess_variants_ab.txt): an
+// XCD-aware workgroup order and requesting the next frame's delta row ahead -- the launch waits neither on L2 hits nor on bytes in flight.
+// The fused launch reads its delta rows straight from global memory: staging them through LDS costs occupancy and is slower
+// (profiles/r07_preprocess_forms_ab.txt).
+// Bucket binning of the calls without shared activation (preprocess_kernel<false>): the bin records are stored at the Gaussian's own index
+// (coalesced lines), the count pass (bin_index_kernel) walks them in index order against a whole-frame LDS tile table, and the scatter pass
+// (bin_kernel) gathers them in Morton order, each XCD taking whole frames.  Records at the Morton slot, or both passes in one order, are
+// slower (profiles/r07_bin_layout_ab.txt).  The shared-activation path keeps its records at the Morton slot.
 constexpr int TILE = GVF_TILE;
 constexpr int BLEND_THREADS = TILE * TILE;
 constexpr int MAX_SH_COEFFS = 16;
@@ -161,7 +128,7 @@ struct PreParams {
     int n_delta;
     int upstream_binning;   // 1: bin the whole 3-sigma tile rect as upstream does
     int F;                  // frames of the call (grid.y covers them PRE_FB at a time)
-    int delta_lds;          // GVF_PRE_DELTA_LDS and the delta rows of a workgroup are whole 16-byte pieces (P even, 16-B aligned tensor)
+    int delta_lds;          // read by no kernel (always 0); kept so that the kernel arguments stay as they are
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -218,10 +185,6 @@ __device__ __forceinline__ float act_log1pf(float y) {      // y >= 0 (or NaN)
     acc = acc + f;
     return acc + dk * 6.9313812256e-1f;
 }
-#ifdef ACT_ABL_LIBM     // timing experiment only (variant build): the device math library's expf / log1pf, as up to round 5 (NOT bit-shared with the oracle)
-#define act_expf expf
-#define act_log1pf log1pf
-#endif
 __device__ __forceinline__ float act_scale(float x, const GvfGaussianActivation& a) {
     float s = a.scaling_activation == 0 ? act_expf(x) : (x > 20.0f ? x : act_log1pf(act_expf(x)));
     return sqrtf(s * s + a.min_kernel_size * a.min_kernel_size);
@@ -476,13 +439,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     const int t = threadIdx.x;
     const int P = pp.P, M = pp.M;
     const int nbx = (P + PRE_THREADS - 1) / PRE_THREADS;
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (GVF_PRE_XCD) {
-        const int FY = (pp.F + PRE_FB - 1) / PRE_FB, k = (int)(blockIdx.x >> 3);
-        bx = (k / FY) * 8 + (int)(blockIdx.x & 7u);
-        by = k - (k / FY) * FY;
-        if (bx >= nbx) return;                  // the grid is rounded up to whole groups of 8 blocks (workgroup-uniform)
-    }
+    const int bx = blockIdx.x, by = blockIdx.y;
     const int i = bx * PRE_THREADS + t;
 
     // Stage this block's SH coefficients through LDS with coalesced 16-byte loads: 256 Gaussians x
@@ -498,86 +455,13 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         for (int k = t; k < n4; k += PRE_THREADS) dst4[k] = src4[k];
         for (int k = (n4 << 2) + t; k < total; k += PRE_THREADS) sh_lds[k] = sh[span0 + k];
     }
-#if GVF_PRE_DELTA_LDS
-    // delta rows through LDS (pp.delta_lds: the span of a workgroup is nvalid * 14 floats, nvalid even, 16-byte aligned): dq 16-byte pieces per frame
-    float* d_lds = sh_lds + ((size_t)PRE_THREADS * sh_stride * 4 + 15) / 16 * 4 + 4;     // behind the SH rows (host: sh_lds_bytes)
-    const bool dstage = !SHARED && pp.delta_lds && pp.fused && delta != nullptr;
-    const int dq = min(PRE_THREADS, P - bx * PRE_THREADS) * 14 / 4;
-    float4 dreg0 = make_float4(0.f, 0.f, 0.f, 0.f), dreg1 = dreg0, dreg2 = dreg0, dreg3 = dreg0;
-    // the frame's delta slice (workgroup-uniform) -> the four pieces of this thread; false: the frame has none
-    auto dfetch = [&](int f_) -> bool {
-        const int di_ = frames[f_].delta_index;
-        if (di_ < 0) return false;
-        const float4* src = reinterpret_cast<const float4*>(delta + ((size_t)di_ * P + (size_t)bx * PRE_THREADS) * 14) + t;
-        if (t < dq) dreg0 = src[0];
-        if (t + PRE_THREADS < dq) dreg1 = src[PRE_THREADS];
-        if (t + 2 * PRE_THREADS < dq) dreg2 = src[2 * PRE_THREADS];
-        if (t + 3 * PRE_THREADS < dq) dreg3 = src[3 * PRE_THREADS];
-        return true;
-    };
-    auto dcommit = [&]() {
-        float4* dst = reinterpret_cast<float4*>(d_lds) + t;
-        if (t < dq) dst[0] = dreg0;
-        if (t + PRE_THREADS < dq) dst[PRE_THREADS] = dreg1;
-        if (t + 2 * PRE_THREADS < dq) dst[2 * PRE_THREADS] = dreg2;
-        if (t + 3 * PRE_THREADS < dq) dst[3 * PRE_THREADS] = dreg3;
-    };
-    bool dcur = false;
-    if (dstage && by * PRE_FB < pp.F) { dcur = dfetch(by * PRE_FB); if (dcur) dcommit(); }
-#endif
     __syncthreads();
 
   const uint32_t my_slot = (bin_slot != nullptr && i < P) ? bin_slot[i] : (uint32_t)i;
-#if GVF_PRE_PREFETCH
-  // the delta row of the NEXT frame of this workgroup is requested before the current frame's arithmetic
-  float dnx[14];
-  bool dnx_has = false;
-  auto fetch_delta = [&](int f_) {
-      dnx_has = false;
-      if (pp.fused && delta != nullptr && i < P && f_ < pp.F) {
-          const int di = frames[f_].delta_index;
-          if (di >= 0) {
-              const float* d = delta + ((size_t)di * P + i) * 14;
-#pragma unroll
-              for (int k = 0; k < 14; ++k) dnx[k] = d[k];
-              dnx_has = true;
-          }
-      }
-      if (!dnx_has) {
-#pragma unroll
-          for (int k = 0; k < 14; ++k) dnx[k] = 0.0f;
-      }
-  };
-  fetch_delta(by * PRE_FB);
-#endif
   for (int ff = 0; ff < PRE_FB; ++ff) {
     const int f = by * PRE_FB + ff;
     if (f >= pp.F) break;
     const GvfRastFrame* fr = frames + f;
-#if GVF_PRE_DELTA_LDS
-    float drow[14];
-    if (dstage) {
-        if (dcur && i < P) {
-#pragma unroll
-            for (int k = 0; k < 14; ++k) drow[k] = d_lds[t * 14 + k];
-        } else {
-#pragma unroll
-            for (int k = 0; k < 14; ++k) drow[k] = 0.0f;
-        }
-    }
-    bool dnext = false;
-    if (dstage && ff + 1 < PRE_FB && f + 1 < pp.F) {      // uniform
-        __syncthreads();                                  // every row of frame ff has left the buffer
-        dnext = dfetch(f + 1);                            // in flight during this frame's arithmetic
-    }
-#endif
-#if GVF_PRE_PREFETCH
-    float dcur[14];
-#pragma unroll
-    for (int k = 0; k < 14; ++k) dcur[k] = dnx[k];
-    const bool dcur_has = dnx_has;
-    if (ff + 1 < PRE_FB) fetch_delta(f + 1);
-#endif
     uint32_t touched = 0;
     int radius_out = 0;
     float4 gA = make_float4(0.f, 0.f, 0.f, 0.f), gB = gA, gC = gA;
@@ -593,23 +477,9 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
             c6s[0] = r1.x; c6s[1] = r1.y; c6s[2] = r1.z; c6s[3] = r1.w; c6s[4] = r2.x; c6s[5] = r2.y;
             dadd[0] = r2.z; dadd[1] = r2.w; dadd[2] = r3v.x;
         } else if (pp.fused) {
-#if GVF_PRE_PREFETCH
-            ActGaussian g = activate_vals(i, pp.act, a0, a1, a2, a3, dcur, dcur_has);
-#elif GVF_PRE_DELTA_LDS
-            bool dhas = dcur;
-            if (!dstage) {                                // the row straight from global memory (activate_one's form)
-                const int di = fr->delta_index;
-                const float* d = (delta != nullptr && di >= 0) ? delta + ((size_t)di * P + i) * 14 : nullptr;
-#pragma unroll
-                for (int k = 0; k < 14; ++k) drow[k] = d ? d[k] : 0.0f;
-                dhas = d != nullptr;
-            }
-            ActGaussian g = activate_vals(i, pp.act, a0, a1, a2, a3, drow, dhas);
-#else
             const int di = fr->delta_index;
             const float* d = (delta != nullptr && di >= 0) ? delta + ((size_t)di * P + i) * 14 : nullptr;
             ActGaussian g = activate_one(i, pp.act, a0, a1, a2, a3, d);
-#endif
 #pragma unroll
             for (int k = 0; k < 3; ++k) { p[k] = g.p[k]; s[k] = g.s[k]; dadd[k] = g.drgb[k]; }
 #pragma unroll
@@ -723,14 +593,6 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
             }
         }
         const size_t o = (size_t)f * P + i;
-#if defined(PRE_ABL_NOREC)      // timing experiment: no record stores (one dword keeps the arithmetic alive)
-        if (touched != 0 && gA.x == 12345.678f) splats[4 * o] = gA;
-#else
-        if (!GVF_PRE_REC_QUAD && touched != 0) {   // records of culled Gaussians are never read (no instance refers to them)
-            float4* rec = splats + 4 * o;
-            rec[0] = gA; rec[1] = gB; rec[2] = gC;
-        }
-#endif
         if (tiles_touched != nullptr) tiles_touched[o] = touched;   // radix binning only
         if (radii != nullptr) {
             // slot order (SHARED with a1 = the slot -> Gaussian table): thread i works on slot i, the radii stay indexed by Gaussian
@@ -745,39 +607,32 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
                 const float2 zr = zrange[f];
                 slab = (uint32_t)fminf(fmaxf((gC.y - zr.x) * zr.y, 0.0f), (float)(NSLAB - 1));
             }
-#if defined(PRE_ABL_NOBIN)      // timing experiment: no bin-record stores
-            if (gC.y == 12345.678f)
-#endif
             binrec[(size_t)f * P + my_slot] = make_uint4((uint32_t)rect.x0 | ((uint32_t)rect.y0 << 16),
                                                          (uint32_t)rect.x1 | ((uint32_t)rect.y1 << 16), __float_as_uint(gC.y), slab);
         }
     }
 
-#if !defined(PRE_ABL_NOREC)
-    if (GVF_PRE_REC_QUAD) {
-        // Quad-transposed record store: lane 4 g + j writes piece j (16 bytes; piece 3 = the padding) of the records of lanes
-        // 4 g + k, k = 0 .. 3, so ONE instruction stores 16 whole 64-byte lines where the per-lane form stores 64 quarter lines three times (48 of a
-        // line's 64 bytes, masked at the memory side).  The launch is bound by its stores (no record stores: -26 %, no bin-record stores: -21 %,
-        // profiles/r05_preprocess_store_ablation.txt); this form: live job 146-148 -> 141-142 ms per sample.  All 64 lanes run it (a lane past P or
-        // with a culled Gaussian has touched = 0 and zero pieces), lanes of a quad exchange through DPP quad broadcasts.
-        const int lj = t & 3;
-        float4* qbase = splats + 4 * ((size_t)f * P + (size_t)(i & ~3));
+    // Quad-transposed record store: lane 4 g + j writes piece j (16 bytes; piece 3 = the padding) of the records of lanes
+    // 4 g + k, k = 0 .. 3, so ONE instruction stores 16 whole 64-byte lines where the per-lane form stores 64 quarter lines three times (48 of a
+    // line's 64 bytes, masked at the memory side).  The launch is bound by its stores (no record stores: -26 %, no bin-record stores: -21 %,
+    // profiles/r05_preprocess_store_ablation.txt); this form: live job 146-148 -> 141-142 ms per sample.  All 64 lanes run it (a lane past P or
+    // with a culled Gaussian has touched = 0 and zero pieces), lanes of a quad exchange through DPP quad broadcasts.
+    const int lj = t & 3;
+    float4* qbase = splats + 4 * ((size_t)f * P + (size_t)(i & ~3));
 #define GVF_QB(v_, k_) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, (v_)), (k_) * 0x55, 0xF, 0xF, true))
 #define GVF_QSTORE(k_)                                                                                          \
-        {                                                                                                       \
-            const int tk = __builtin_amdgcn_mov_dpp((int)touched, (k_) * 0x55, 0xF, 0xF, true);                 \
-            float4 o4;                                                                                          \
-            { const float a = GVF_QB(gA.x, k_), b = GVF_QB(gB.x, k_), c = GVF_QB(gC.x, k_); o4.x = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
-            { const float a = GVF_QB(gA.y, k_), b = GVF_QB(gB.y, k_), c = GVF_QB(gC.y, k_); o4.y = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
-            { const float a = GVF_QB(gA.z, k_), b = GVF_QB(gB.z, k_), c = GVF_QB(gC.z, k_); o4.z = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
-            { const float a = GVF_QB(gA.w, k_), b = GVF_QB(gB.w, k_), c = GVF_QB(gC.w, k_); o4.w = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
-            if (tk != 0) qbase[4 * (k_) + lj] = o4;                                                             \
-        }
-        GVF_QSTORE(0) GVF_QSTORE(1) GVF_QSTORE(2) GVF_QSTORE(3)
+    {                                                                                                       \
+        const int tk = __builtin_amdgcn_mov_dpp((int)touched, (k_) * 0x55, 0xF, 0xF, true);                 \
+        float4 o4;                                                                                          \
+        { const float a = GVF_QB(gA.x, k_), b = GVF_QB(gB.x, k_), c = GVF_QB(gC.x, k_); o4.x = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
+        { const float a = GVF_QB(gA.y, k_), b = GVF_QB(gB.y, k_), c = GVF_QB(gC.y, k_); o4.y = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
+        { const float a = GVF_QB(gA.z, k_), b = GVF_QB(gB.z, k_), c = GVF_QB(gC.z, k_); o4.z = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
+        { const float a = GVF_QB(gA.w, k_), b = GVF_QB(gB.w, k_), c = GVF_QB(gC.w, k_); o4.w = lj == 0 ? a : (lj == 1 ? b : (lj == 2 ? c : 0.f)); } \
+        if (tk != 0) qbase[4 * (k_) + lj] = o4;                                                             \
+    }
+    GVF_QSTORE(0) GVF_QSTORE(1) GVF_QSTORE(2) GVF_QSTORE(3)
 #undef GVF_QSTORE
 #undef GVF_QB
-    }
-#endif
 
     // block sum of tiles_touched (feeds the instance-offset scan, R2; radix binning only)
     if (block_sums != nullptr) {
@@ -789,10 +644,6 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         __syncthreads();
         if (t == 0) block_sums[(size_t)f * nbx + bx] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     }
-#if GVF_PRE_DELTA_LDS
-    if (dnext) { dcommit(); __syncthreads(); }            // uniform; the next frame reads the buffer
-    dcur = dnext;
-#endif
   }
 }
 
@@ -903,9 +754,6 @@ constexpr int SORT_SMALL_N = GVF_SORT_SMALL_N;
 static_assert(SORT_SMALL_N == 1536 || SORT_SMALL_N == 2048, "register class of the per-tile sort: 6 or 8 keys per thread");
 constexpr int SORT_LARGE_N = 16384;
 constexpr int SORT_LARGE_BLOCKS = 256, SORT_HUGE_BLOCKS = 64;   // grid of the launch that walks the two rare classes
-#ifndef SORT_LIST_BIT
-#define SORT_LIST_BIT 1
-#endif
 constexpr int SORT_MEDIUM_N = 4096, SORT_MEDIUM_BLOCKS = 768;   // the LDS class's lower half has a launch of its own (tile_sort_kernel<1>)
 __global__ __launch_bounds__(1024) void seg_sums_kernel(const uint32_t* __restrict__ cnt, int n, uint32_t* __restrict__ partial) {
     __shared__ uint32_t wsum[16];
@@ -1012,7 +860,7 @@ __global__ void frame_zrange_kernel(const GvfRastFrame* __restrict__ frames, int
 // scatter pass: cursor allocation, the base is left in the table and an LDS counter hands out the slots).  A block
 // whose window exceeds WIN_MAX tiles (incoherent order) pays one global atomic per instance instead.
 // rec_by_id = 0: the records sit at their slots (preprocess_kernel's bin_slot) and are read as one stream; 1: they sit at the Gaussian's index
-// and are gathered (GVF_BIN_ALGO 1-3), and xcd_frames = 1 then lays the grid out 1-D so that each XCD takes whole frames (see the host).
+// and are gathered, and xcd_frames = 1 then lays the grid out 1-D so that each XCD takes whole frames (see the host).
 constexpr int WIN_MAX = 2048;
 constexpr int BIN_SPT = 4;
 constexpr int BIN_SLOTS = PRE_THREADS * BIN_SPT;
@@ -1118,69 +966,49 @@ __global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy,
     }
 }
 
-// Count / scatter passes in index order (GVF_BIN_ALGO 2): a workgroup takes BINX_PER_WG consecutive Gaussians of one frame, whose bin records
-// preprocess_kernel<false> stored at their own index, and counts their instances in a whole-frame LDS table of (tile, slab) segments, so
-// that every touched segment costs ONE global atomic per workgroup however the Gaussians are ordered in space.  The scatter pass counts
-// again, allocates each segment's run with that atomic and hands out the places from an LDS counter.  The host takes this path only when
-// the frame's segments fit the table (ntiles * nslab <= BINX_TAB).
+// Count pass in index order: a workgroup takes BINX_PER_WG consecutive Gaussians of one frame, whose bin records preprocess_kernel<false>
+// stored at their own index, and counts their instances in a whole-frame LDS table of (tile, slab) segments, so that every touched segment
+// costs ONE global atomic per workgroup however the Gaussians are ordered in space.  The host takes this path only when the frame's segments
+// fit the table (ntiles * nslab <= BINX_TAB).  cursor, total, payload, frame_base and num_rendered are read by no code; they keep the
+// kernel's arguments as they were when it also had a scatter form.
 constexpr int BINX_THREADS = 512;
 constexpr int BINX_TAB = 4096;
 constexpr int BINX_PER_WG = 8192;
 constexpr int BINX_SPT = 4;                          // records in flight per thread
 
-template <bool SCATTER>
 __global__ __launch_bounds__(BINX_THREADS) void bin_index_kernel(int P, int gx, const uint4* __restrict__ binrec,
-                                                                 uint32_t* __restrict__ tile_count /* count pass */,
-                                                                 uint32_t* __restrict__ cursor /* scatter pass */,
+                                                                 uint32_t* __restrict__ tile_count,
+                                                                 uint32_t* __restrict__ cursor,
                                                                  const uint32_t* __restrict__ total,
                                                                  uint64_t* __restrict__ payload, int nslab, int nseg_frame,
                                                                  const uint32_t* __restrict__ frame_base, uint32_t* __restrict__ num_rendered) {
     __shared__ uint32_t s_tab[BINX_TAB];
-    __shared__ uint32_t s_run[SCATTER ? BINX_TAB : 1];
     const int t = threadIdx.x, f = blockIdx.y;
-    if (SCATTER && num_rendered != nullptr && blockIdx.x == 0 && t == 0) num_rendered[f] = frame_base[f + 1] - frame_base[f];
-    if (SCATTER && *total == 0u) return;            // nothing visible, or capacity overflow (uniform)
     const int g0 = (int)blockIdx.x * BINX_PER_WG, g1 = min(P, g0 + BINX_PER_WG);
     const uint4* rec = binrec + (size_t)f * P;
-    for (int e = t; e < nseg_frame; e += BINX_THREADS) { s_tab[e] = 0u; if (SCATTER) s_run[e] = 0u; }
+    for (int e = t; e < nseg_frame; e += BINX_THREADS) s_tab[e] = 0u;
     __syncthreads();
-    // one sweep over the workgroup's records: PASS 0 counts into s_tab, PASS 1 (scatter) writes the keys at s_tab[e] + run
-    auto sweep = [&](auto pass) {
-        for (int base = g0; base < g1; base += BINX_SPT * BINX_THREADS) {
-            uint4 br[BINX_SPT];
+    for (int base = g0; base < g1; base += BINX_SPT * BINX_THREADS) {
+        uint4 br[BINX_SPT];
 #pragma unroll
-            for (int k = 0; k < BINX_SPT; ++k) {
-                const int s = base + k * BINX_THREADS + t;
-                br[k] = s < g1 ? rec[s] : make_uint4(0u, 0u, 0u, 0u);     // {0, 0, 0, 0}: an empty rect
-            }
-#pragma unroll
-            for (int k = 0; k < BINX_SPT; ++k) {
-                const int x0 = (int)(br[k].x & 0xffffu), y0 = (int)(br[k].x >> 16);
-                const int x1 = (int)(br[k].y & 0xffffu), y1 = (int)(br[k].y >> 16);
-                const int sl = (int)br[k].w;
-                const uint64_t key = ((uint64_t)br[k].z << 32) | (uint32_t)(base + k * BINX_THREADS + t);   // depth bits above the Gaussian id
-                for (int y = y0; y < y1; ++y)
-                    for (int x = x0; x < x1; ++x) {
-                        const int e = (y * gx + x) * nslab + sl;
-                        if constexpr (decltype(pass)::value == 0) atomicAdd(&s_tab[e], 1u);
-                        else payload[s_tab[e] + atomicAdd(&s_run[e], 1u)] = key;
-                    }
-            }
+        for (int k = 0; k < BINX_SPT; ++k) {
+            const int s = base + k * BINX_THREADS + t;
+            br[k] = s < g1 ? rec[s] : make_uint4(0u, 0u, 0u, 0u);     // {0, 0, 0, 0}: an empty rect
         }
-    };
-    sweep(std::integral_constant<int, 0>{});
-    __syncthreads();
-    uint32_t* gtab = (SCATTER ? cursor : tile_count) + (size_t)f * nseg_frame;   // [tile][slab]
-    for (int e = t; e < nseg_frame; e += BINX_THREADS) {
-        const uint32_t c = s_tab[e];
-        if (c != 0u) {
-            if (SCATTER) s_tab[e] = atomicAdd(&gtab[e], c);
-            else atomicAdd(&gtab[e], c);
+#pragma unroll
+        for (int k = 0; k < BINX_SPT; ++k) {
+            const int x0 = (int)(br[k].x & 0xffffu), y0 = (int)(br[k].x >> 16);
+            const int x1 = (int)(br[k].y & 0xffffu), y1 = (int)(br[k].y >> 16);
+            const int sl = (int)br[k].w;
+            for (int y = y0; y < y1; ++y)
+                for (int x = x0; x < x1; ++x) atomicAdd(&s_tab[(y * gx + x) * nslab + sl], 1u);
         }
     }
-    if (SCATTER) {
-        __syncthreads();
-        sweep(std::integral_constant<int, 1>{});
+    __syncthreads();
+    uint32_t* gtab = tile_count + (size_t)f * nseg_frame;   // [tile][slab]
+    for (int e = t; e < nseg_frame; e += BINX_THREADS) {
+        const uint32_t c = s_tab[e];
+        if (c != 0u) atomicAdd(&gtab[e], c);
     }
 }
 
@@ -1264,8 +1092,8 @@ __global__ __launch_bounds__(1024) void morton_scan_kernel(uint32_t* __restrict_
     for (int k = 0; k < PER; ++k) { hist[t * PER + k] = run; run += v[k]; }
 }
 
-// codes_rank: in = the Gaussian's Morton code, out = its slot in the order (the inverse permutation: the shared-activation launch, and
-// the fused one under GVF_BIN_ALGO 0, write the bin records at their slots, so the bin passes read them as one contiguous stream)
+// codes_rank: in = the Gaussian's Morton code, out = its slot in the order (the inverse permutation: the shared-activation launch writes
+// the bin records at their slots, so the bin passes read them as one contiguous stream)
 __global__ __launch_bounds__(256) void morton_scatter_kernel(int P, uint32_t* codes_rank, uint32_t* __restrict__ hist,
                                                              uint32_t* __restrict__ order) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1304,10 +1132,6 @@ __global__ __launch_bounds__(256) void ranges_kernel(const uint64_t* __restrict_
 // (slow, correct: a whole scene projected onto one tile).  All three are launched over all tiles; a
 // workgroup whose segment is not in its class exits at once.
 // ---------------------------------------------------------------------------------------------
-#ifndef SORT_BUCKETS
-#define SORT_BUCKETS 1            // 0: every small segment through the sorting network (the round-1 path)
-#endif
-
 // Bitonic sorting network in its "all comparators ascending" form (the first step of every merge compares
 // mirrored partners i <-> block_end - i, the remaining steps are the usual half-cleaners).  Because every
 // compare-exchange puts the larger key at the higher index, virtual +inf padding above n never moves: pairs
@@ -1587,7 +1411,7 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, MODE == 3 ? 2 : 1) void til
         const uint64_t* k = keys + rng.x;
         const uint32_t* v = vals != nullptr ? vals + rng.x : nullptr;
         uint32_t* o = ids + rng.x;
-        if (SORT_BUCKETS && n > 128) {               // distribution sort; false = a long run of near-equal depths, take the network
+        if (n > 128) {                               // distribution sort (profiles/r02f_tile_sort_ubench.txt); false = a long run of near-equal depths, take the network
             bool done;
             if (n <= 256) done = tile_sort_buckets<1, 256, 1>(k, v, o, n, s_small, s_hist);
             else if (n <= 512) done = tile_sort_buckets<2, 256, 2>(k, v, o, n, s_small, s_hist);
@@ -1644,17 +1468,12 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, MODE == 3 ? 2 : 1) void til
     for (uint32_t li = bid; li < count; li += stride) {
         // the LDS class's list says in its top bit which half an entry belongs to: the launch that does NOT own a segment skips it on the list word
         // alone (round 5: it used to read the segment's range first -- a dependent global load per skipped entry; the 1024-thread launch walked
-        // ~80 entries per workgroup to find its few: 75 us per live chunk, mostly that)
+        // ~80 entries per workgroup to find its few: 75 us per live chunk, mostly that; profiles/r05_sort_list_bit_ab.txt)
         const uint32_t ent = list[li];
         const bool upper = !huge && (ent >> 31) != 0u;
-#if SORT_LIST_BIT
         if (!huge && ((MODE == 3 && upper) || (MODE == 1 && split != 0u && !upper))) continue;       // the other launch's segment
-#endif
         const uint2 rng = ranges[huge ? ent : (ent & 0x7fffffffu)];
         const int n = (int)(rng.y - rng.x);
-#if !SORT_LIST_BIT                 // A/B switch: the round-4 form (decide on the range)
-        if ((MODE == 3 && n > SORT_MEDIUM_N) || (MODE == 1 && !huge && split != 0u && n <= SORT_MEDIUM_N)) continue;
-#endif
         uint64_t* k = keys + rng.x;
         const uint32_t* v = vals != nullptr ? vals + rng.x : nullptr;
         if (huge) {
@@ -1664,12 +1483,12 @@ __global__ __launch_bounds__(MODE == 3 ? 512 : 1024, MODE == 3 ? 2 : 1) void til
             bitonic_sort_asc(k, n, tid, nt);
             for (int i = tid; i < n; i += nt) ids[rng.x + i] = (uint32_t)k[i];
         } else {
-            if (MODE == 3 && SORT_BUCKETS) {             // the distribution sort on 512 threads
+            if (MODE == 3) {                             // the distribution sort on 512 threads
                 const bool sorted = tile_sort_buckets<8, 512, BKT_LARGE_NB / 512>(k, v, ids + rng.x, n, s_large, s_hist);
                 __syncthreads();
                 if (sorted) continue;
             }
-            if (MODE == 1 && SORT_BUCKETS) {             // the distribution sort on 1024 threads; false = crowded bucket, take the network
+            if (MODE == 1) {                             // the distribution sort on 1024 threads; false = crowded bucket, take the network
                 bool sorted;
                 if (n <= 4096) sorted = tile_sort_buckets<4, 1024, BKT_LARGE_NB / 1024>(k, v, ids + rng.x, n, s_large, s_hist);
                 else if (n <= 8192) sorted = tile_sort_buckets<8, 1024, BKT_LARGE_NB / 1024>(k, v, ids + rng.x, n, s_large, s_hist);
@@ -1706,14 +1525,12 @@ static int launch_tile_sort(hipStream_t stream, const uint2* ranges, uint64_t* k
         hipLaunchKernelGGL(classify_kernel, dim3((nseg + 255) / 256), dim3(256), 0, stream, ranges, nseg, cls);
     hipLaunchKernelGGL(tile_sort_kernel<0>, dim3(nseg), dim3(256), 0, stream, ranges, keys, vals, ids, cls, nseg);
     if (tile_sort_set_lds_limit() != GVF_OK) return GVF_ELAUNCH;
-    // the LDS class up to SORT_MEDIUM_N keys: three workgroups of 512 threads per CU (GVF_TILE_SORT_MEDIUM=0: measurement switch)
-    static const bool medium = [] { const char* e = getenv("GVF_TILE_SORT_MEDIUM"); return !(e && e[0] == '0'); }();
-    if (medium)
-        hipLaunchKernelGGL(tile_sort_kernel<3>, dim3(SORT_MEDIUM_BLOCKS), dim3(512), SORT_MEDIUM_N * 8, stream, ranges, keys, vals, ids, cls,
-                           nseg, 0u);
+    // the LDS class up to SORT_MEDIUM_N keys: three workgroups of 512 threads per CU (profiles/r04c_live_render.txt)
+    hipLaunchKernelGGL(tile_sort_kernel<3>, dim3(SORT_MEDIUM_BLOCKS), dim3(512), SORT_MEDIUM_N * 8, stream, ranges, keys, vals, ids, cls,
+                       nseg, 0u);
     // the rest of it and the global class in one launch
     hipLaunchKernelGGL(tile_sort_kernel<1>, dim3(SORT_LARGE_BLOCKS + SORT_HUGE_BLOCKS), dim3(1024), SORT_LARGE_N * 8, stream, ranges, keys,
-                       vals, ids, cls, nseg, medium ? 1u : 0u);
+                       vals, ids, cls, nseg, 1u);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
 }
@@ -1856,42 +1673,12 @@ extern "C" int gvf_debug_blend_consumed(unsigned long long* out12, int reset) {
 }
 #endif
 
-// The pixel's "done" flag of blend_kernel (outside the image, or saturated) and the predicates of its compositing step.
-// GVF_BLEND_LANE_MASKS = 1 (round 6, the product): the flag lives as the wave's 64-bit LANE MASK and the predicates are scalar operations on lane
-// masks (ballot / inverse ballot).  As a per-lane bool (= 0, the form up to round 6, kept as the A/B variant) the compiler holds the same masks in
-// scalar registers but pays one scalar instruction more per list entry (the complement of `done`) and rebuilds the flag in a vector register for
-// every __all() (v_cndmask + v_cmp per trip); scalar instructions come out of the same wave's issue stream as the vector ones (a s_waitcnt does
-// not: scripts/ubench/blend_step.hip MODE 4).  The loop alone: 41.4 -> 38.9 ticks per list entry per SIMD (MODE 2 there,
-// profiles/r06_ubench_blend_step.txt).  Same arithmetic, same decisions: images are bit-identical.  The fence between the two pairs of a trip
-// keeps the second pair's LDS reads behind the first pair's arithmetic: without it the scheduler requests all four entries' records at once --
-// 68 vector registers, seven waves per SIMD instead of eight.
-#ifndef GVF_BLEND_LANE_MASKS
-#define GVF_BLEND_LANE_MASKS 1
-#endif
-#ifndef GVF_BLEND_FIRST_ROUND_REDUCE       // 1: the workgroup-wide "every pixel saturated?" reduction runs before the first round too (the form up to round 6; A/B variant)
-#define GVF_BLEND_FIRST_ROUND_REDUCE 0
-#endif
-#if GVF_BLEND_LANE_MASKS
-#define BL_DONE_INIT(init) unsigned long long done_m = __builtin_amdgcn_ballot_w64(init)      /* all 64 lanes are active: workgroups are whole */
-#define BL_WAVE_DONE() (done_m == ~0ull)
-#define BL_WORKGROUP_DONE() __syncthreads_and(done_m == ~0ull)
-#define BL_STEP_PREDICATES(alpha, test_T)                                                                   \
-            const unsigned long long ok_m = __builtin_amdgcn_ballot_w64(!((alpha) < 1.0f / 255.0f)) & ~done_m;   \
-            const unsigned long long stop_m = ok_m & __builtin_amdgcn_ballot_w64((test_T) < 0.0001f);       \
-            done_m |= stop_m;                                                                               \
-            const bool acc = __builtin_amdgcn_inverse_ballot_w64(ok_m ^ stop_m);
-#define BL_PAIR_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define BL_DONE_INIT(init) bool done = (init)
-#define BL_WAVE_DONE() __all(done)
-#define BL_WORKGROUP_DONE() (__syncthreads_count(done) == BLEND_THREADS)
-#define BL_STEP_PREDICATES(alpha, test_T)                                                                   \
-            const bool ok = !done && !((alpha) < 1.0f / 255.0f);                                            \
-            const bool stop = ok && (test_T) < 0.0001f;                                                     \
-            done = done || stop;                                                                            \
-            const bool acc = ok != stop;           /* = ok && !stop (stop implies ok): a scalar xor of the two lane masks instead of a second compare */
-#define BL_PAIR_FENCE() do { } while (0)
-#endif
+// The pixel's "done" flag of blend_kernel (outside the image, or saturated) lives as the wave's 64-bit LANE MASK done_m, and the predicates of
+// the compositing step are scalar operations on lane masks (ballot / inverse ballot); all 64 lanes are active, workgroups are whole.  A per-lane
+// bool costs one scalar instruction more per list entry and a vector rebuild of the flag per __all(): 41.4 against 38.9 ticks per list entry per
+// SIMD in the loop alone (profiles/r06_ubench_blend_step.txt, r06_blend_lane_masks_ab.txt), bit-identical images.  The fence between the two
+// pairs of a trip keeps the second pair's LDS reads behind the first pair's arithmetic: without it the scheduler requests all four entries'
+// records at once -- 68 vector registers, seven waves per SIMD instead of eight.
 
 // DEPTH: accumulate the depth channel (diff_gauss outputs; one fma per evaluated splat that the mip path does not pay)
 template <bool DEPTH>
@@ -1931,7 +1718,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
     const uint64_t lt_mask = (1ull << lane) - 1ull;
 
     const float pxr = pxf - (float)(tx * TILE), pyr = pyf - (float)(ty * TILE);      // tile-relative (exact: small integers + the sub-pixel offset)
-    BL_DONE_INIT(!inside);
+    unsigned long long done_m = __builtin_amdgcn_ballot_w64(!inside);
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dacc = 0.f;
 
     BT_DECL
@@ -1941,11 +1728,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
     for (int r = 0; r < rounds; ++r, todo -= BLEND_THREADS) {
         BT(6);
         // (r > 0: before the first round no pixel inside the image is saturated and nothing in LDS has to be protected from a previous round;
-        //  the reduction's LDS round trip and barriers are ~1 % of a wave's life at 1.17 rounds per tile)
+        //  the reduction's LDS round trip and barriers are ~1 % of a wave's life at 1.17 rounds per tile, profiles/r06_blend_lane_masks_ab.txt)
 #ifdef BLEND_CONSUMED
-        if ((GVF_BLEND_FIRST_ROUND_REDUCE || r > 0) && BL_WORKGROUP_DONE()) { rounds_done = r; break; }
+        if (r > 0 && __syncthreads_and(done_m == ~0ull)) { rounds_done = r; break; }
 #else
-        if ((GVF_BLEND_FIRST_ROUND_REDUCE || r > 0) && BL_WORKGROUP_DONE()) break;
+        if (r > 0 && __syncthreads_and(done_m == ~0ull)) break;
 #endif
         BT(0);
 #ifdef BLEND_TIMING
@@ -1987,7 +1774,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
         __syncthreads();
         BT(4);
         const int cnt = min(BLEND_THREADS, todo);
-        if (BL_WAVE_DONE()) continue;                     // this quadrant is saturated (wave-uniform)
+        if (done_m == ~0ull) continue;                    // this quadrant is saturated (wave-uniform)
         // compact the batch into this wave's list (ascending index = depth order)
         int n_w = 0;
 #pragma unroll
@@ -2016,7 +1803,11 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
             const float alpha = fminf(0.99f, __builtin_amdgcn_exp2f(-nlog));                           \
             const float w_raw = alpha * T;                                                             \
             const float test_T = T - w_raw;        /* = T (1 - alpha) up to one rounding; one op less */ \
-            BL_STEP_PREDICATES(alpha, test_T)      /* ok = !done && !(alpha < 1/255); stop = ok && test_T < 1e-4; done |= stop; acc = ok && !stop */ \
+            /* ok = !done && !(alpha < 1/255); stop = ok && test_T < 1e-4; done |= stop; acc = ok && !stop */                  \
+            const unsigned long long ok_m = __builtin_amdgcn_ballot_w64(!(alpha < 1.0f / 255.0f)) & ~done_m;   \
+            const unsigned long long stop_m = ok_m & __builtin_amdgcn_ballot_w64(test_T < 0.0001f);    \
+            done_m |= stop_m;                                                                          \
+            const bool acc = __builtin_amdgcn_inverse_ballot_w64(ok_m ^ stop_m);                       \
             const float wgt = acc ? w_raw : 0.0f;                                                      \
             C0 = __builtin_fmaf(b.z, wgt, C0);                                                         \
             C1 = __builtin_fmaf(b.w, wgt, C1);                                                         \
@@ -2026,16 +1817,16 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
         }
         int jj = 0;
         for (; jj + 3 < n_w; jj += 4) {
-            if (BL_WAVE_DONE()) break;
+            if (done_m == ~0ull) break;
             const unsigned j0 = sList[wave][jj], j1 = sList[wave][jj + 1], j2 = sList[wave][jj + 2], j3 = sList[wave][jj + 3];
             GVF_BLEND_STEP(j0)
             GVF_BLEND_STEP(j1)
-            BL_PAIR_FENCE();
+            __builtin_amdgcn_sched_barrier(0);
             GVF_BLEND_STEP(j2)
             GVF_BLEND_STEP(j3)
         }
         for (; jj < n_w; ++jj) {
-            if (BL_WAVE_DONE()) break;
+            if (done_m == ~0ull) break;
             const unsigned j0 = sList[wave][jj];
             GVF_BLEND_STEP(j0)
         }
@@ -2051,11 +1842,7 @@ __global__ __launch_bounds__(BLEND_THREADS) void blend_kernel(
     if (inside) {
         const size_t hw = (size_t)H * W;
         const float r0 = __builtin_fmaf(T, bg0, C0), r1 = __builtin_fmaf(T, bg1, C1), r2 = __builtin_fmaf(T, bg2, C2);
-#ifdef BLEND_ABL_NO_U8      // timing experiment only (variant build): the epilogue without the uint8 form
-        if (false) {
-#else
-        if (out_u8 != nullptr) {                   // (uniform) round 6: no fp32 frame in HBM at all when the caller wants the uint8 one
-#endif
+        if (out_u8 != nullptr) {                   // (uniform) no fp32 frame in HBM at all when the caller wants the uint8 one
             unsigned char* ob = out_u8 + (size_t)f * 3 * hw;
             ob[0 * hw + pid] = (unsigned char)(fminf(fmaxf(r0, 0.f), 1.f) * 255.0f);
             ob[1 * hw + pid] = (unsigned char)(fminf(fmaxf(r1, 0.f), 1.f) * 255.0f);
@@ -2271,11 +2058,9 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         // worth it from two frames per slice on; the records must fit into keys_alt
         if (shared && (F < 2 * slices.n || (size_t)slices.n * (size_t)P * 64u > (size_t)(max_rendered > 0 ? max_rendered : 0) * 8u)) shared = false;
     }
-    // bucket binning without shared activation (GVF_BIN_ALGO): bin_index_kernel takes the count pass (2, 3) and the scatter pass (3) when a
-    // frame's (tile, slab) segments fit its table
-    const bool index_fits = st.bin_algo != GVF_RAST_BIN_RADIX && !shared && (size_t)ntiles * NSLAB <= (size_t)BINX_TAB;
-    const bool index_count = GVF_BIN_ALGO >= 2 && index_fits, index_scatter = GVF_BIN_ALGO == 3 && index_fits;
-    const bool morton = st.bin_algo != GVF_RAST_BIN_RADIX && F >= 4 && P >= 4096 && !index_scatter;   // spatial order of the Gaussians (see below)
+    // bucket binning without shared activation: bin_index_kernel takes the count pass when a frame's (tile, slab) segments fit its table
+    const bool index_count = st.bin_algo != GVF_RAST_BIN_RADIX && !shared && (size_t)ntiles * NSLAB <= (size_t)BINX_TAB;
+    const bool morton = st.bin_algo != GVF_RAST_BIN_RADIX && F >= 4 && P >= 4096;   // spatial order of the Gaussians (see below)
     // slot order of the shared-activation path (see activate_cov_kernel): needs the Morton order, SH input and room for the slot-ordered SH copy
     // behind the records.  Decided here, in front of the upload launch, which records it for the backward (LAYOUT_WORD).
     // GVF_RAST_SLOT_ORDER=0: measurement / test switch
@@ -2330,8 +2115,8 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         }
         // depth slabs need the scene's depth range, which comes with the Morton stage: one slab otherwise
         const int nslab = order != nullptr ? NSLAB : 1;
-        // GVF_BIN_ALGO 1-3: preprocess_kernel<false> stores the bin records at the Gaussians' indices, bin_kernel gathers them in Morton order
-        const bool rec_gather = GVF_BIN_ALGO >= 1 && bucket && !shared && order != nullptr;
+        // preprocess_kernel<false> stores the bin records at the Gaussians' indices, bin_kernel gathers them in Morton order
+        const bool rec_gather = bucket && !shared && order != nullptr;
         nslab_blend = nslab;
         const unsigned nseg = (unsigned)((size_t)F * ntiles * nslab);
         prof_mark(stream, slot, 1);
@@ -2343,10 +2128,8 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         pp.upstream_binning = (st.upstream_binning != 0 || subpixel_offset != nullptr) ? 1 : 0;
         if (fused) pp.act = *act; else pp.act = GvfGaussianActivation{};
         const size_t sh_lds_bytes = gvf_align_up((size_t)PRE_THREADS * pp.M * 3 * sizeof(float), 16) + 16;
-        pp.delta_lds = (GVF_PRE_DELTA_LDS && fused && delta != nullptr && P % 2 == 0 && (((uintptr_t)delta) & 15) == 0) ? 1 : 0;
-        const size_t pre_lds_bytes = sh_lds_bytes + (pp.delta_lds ? (size_t)PRE_THREADS * 14 * sizeof(float) : 0);   // + the delta rows
-        const int pre_fy = (F + PRE_FB - 1) / PRE_FB;
-        const dim3 pre_grid = GVF_PRE_XCD ? dim3((nb + 7) / 8 * 8 * pre_fy) : dim3(nb, pre_fy);
+        pp.delta_lds = 0;
+        const dim3 pre_grid(nb, (F + PRE_FB - 1) / PRE_FB);
         if (shared) {
             g_shared_calls.fetch_add(1, std::memory_order_relaxed);
             float4* rec3d = reinterpret_cast<float4*>(w.keys_alt);
@@ -2367,18 +2150,18 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
                                nullptr, nullptr, w.splats, nullptr, out_radii == nullptr ? nullptr : w.radii, nullptr, w.binrec,
                                order != nullptr ? w.order_alt : nullptr, nslab > 1 ? w.zrange : nullptr);
         } else
-        hipLaunchKernelGGL(preprocess_kernel<false>, pre_grid, dim3(PRE_THREADS), pre_lds_bytes, stream, pp,
+        hipLaunchKernelGGL(preprocess_kernel<false>, pre_grid, dim3(PRE_THREADS), sh_lds_bytes, stream, pp,
                            w.frames, a0, a1, a2, a3, colors_precomp ? nullptr : sh, colors_precomp, cov3D_precomp, delta,
                            w.splats, bucket ? nullptr : w.tiles_touched, (bucket && out_radii == nullptr) ? nullptr : w.radii,
                            bucket ? nullptr : w.block_sums, bucket ? w.binrec : nullptr,
-                           (order != nullptr && !rec_gather) ? w.order_alt : nullptr, (bucket && nslab > 1) ? w.zrange : nullptr);
-        // bin passes: index order (bin_index_kernel), or Morton order over records at their slots / gathered from the Gaussians' indices,
-        // the gather with a 1-D grid in which each XCD takes whole frames (bin_kernel).  The count pass only sums per segment, so its walk
-        // need not be the scatter pass's.
+                           nullptr, (bucket && nslab > 1) ? w.zrange : nullptr);
+        // bin passes (bin_kernel): Morton order over records at their slots (shared activation) or gathered from the Gaussians' indices, the
+        // gather with a 1-D grid in which each XCD takes whole frames.  The count pass only sums per segment, so it may walk the records in
+        // index order instead (bin_index_kernel).
         const int bnb = (P + BIN_SLOTS - 1) / BIN_SLOTS, xnb = (P + BINX_PER_WG - 1) / BINX_PER_WG;
         const dim3 bin_grid = rec_gather ? dim3((unsigned)((F + 7) / 8 * 8 * bnb)) : dim3(bnb, F);
         if (index_count)
-            hipLaunchKernelGGL(bin_index_kernel<false>, dim3(xnb, F), dim3(BINX_THREADS), 0, stream, P, gx, w.binrec,
+            hipLaunchKernelGGL(bin_index_kernel, dim3(xnb, F), dim3(BINX_THREADS), 0, stream, P, gx, w.binrec,
                                w.tile_count, w.cursor, w.total, w.keys, nslab, ntiles * nslab, nullptr, nullptr);
         else if (bucket)
             hipLaunchKernelGGL(bin_kernel<false>, bin_grid, dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
@@ -2401,10 +2184,7 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
         GVF_CHECK_LAUNCH();
         prof_mark(stream, slot, 3);
         if (max_rendered > 0) {
-            if (index_scatter)
-                hipLaunchKernelGGL(bin_index_kernel<true>, dim3(xnb, F), dim3(BINX_THREADS), 0, stream, P, gx, w.binrec,
-                                   w.tile_count, w.cursor, w.total, w.keys, nslab, ntiles * nslab, w.frame_base, out_num_rendered);
-            else if (bucket)
+            if (bucket)
                 hipLaunchKernelGGL(bin_kernel<true>, bin_grid, dim3(PRE_THREADS), 0, stream, P, gx, gy, w.binrec, order,
                                    w.tile_count, w.cursor, w.total, w.keys, nslab, w.frame_base, out_num_rendered,
                                    rec_gather ? 1 : 0, rec_gather ? 1 : 0, F);

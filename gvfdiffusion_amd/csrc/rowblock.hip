@@ -115,11 +115,7 @@ __device__ __forceinline__ typename GvfLp<DT>::x8 rb_ldw(const uint4* p) { retur
 // Past the end it repeats its last step (the refills behind the last MFMAs are redundant, never out of bounds).
 struct RbStream {
     const uint4* w; int Gt;
-#if defined(RB_ABL_WSMALL)        // timing experiment: every step reads the same 32 KiB (L1 / L2 hits only)
-    __device__ __forceinline__ const uint4* at(int s) const { return w + (long long)(s & 1) * RB_STEP; }
-#else
     __device__ __forceinline__ const uint4* at(int s) const { return w + (long long)(s < Gt ? s : Gt - 1) * RB_STEP; }
-#endif
 };
 
 // `steps` k-steps (a multiple of D) of acc += act * W: 3 activation fragments per step from LDS (act = block base + lane), 24 MFMAs,
@@ -143,13 +139,7 @@ __device__ __forceinline__ void rb_gemm(f32x4 (&acc)[3][RB_CT], typename GvfLp<D
 #pragma unroll
         for (int b = 0; b < D; ++b) {
 #pragma unroll
-            for (int rt = 0; rt < 3; ++rt) {
-#ifdef RB_ABL_NOLDS                // timing experiment: activation fragments as opaque register values
-                asm volatile("" : "+v"(af[(b + 1) & 1][rt]));
-#else
-                af[(b + 1) & 1][rt] = __builtin_bit_cast(x8, act[((ksl + b + 1) * 3 + rt) * 64]);
-#endif
-            }
+            for (int rt = 0; rt < 3; ++rt) af[(b + 1) & 1][rt] = __builtin_bit_cast(x8, act[((ksl + b + 1) * 3 + rt) * 64]);
             __builtin_amdgcn_sched_barrier(0);   // ... issued BEFORE this step's MFMAs (the scheduler would sink them behind)
             const uint4* sn = st.at(g + b + D);
 #pragma unroll
@@ -157,11 +147,7 @@ __device__ __forceinline__ void rb_gemm(f32x4 (&acc)[3][RB_CT], typename GvfLp<D
 #pragma unroll
                 for (int rt = 0; rt < 3; ++rt)
                     acc[rt][ct] = SWAP ? GvfLp<DT>::mfma16(af[b & 1][rt], wf[b][ct], acc[rt][ct]) : GvfLp<DT>::mfma16(wf[b][ct], af[b & 1][rt], acc[rt][ct]);
-#if defined(RB_ABL_WFRAC)          // timing experiment: only RB_ABL_WFRAC of the 4 column tiles are refilled (what a column split across CUs would leave of the fill traffic)
-                if (ct < RB_ABL_WFRAC) wf[b][ct] = rb_ldw<DT>(sn + ct * 64);
-#elif !defined(RB_ABL_NOW)         // timing experiment: no weight refills at all
                 wf[b][ct] = rb_ldw<DT>(sn + ct * 64);
-#endif
             }
             __builtin_amdgcn_sched_barrier(0);   // the refills stay in the step that frees their registers
         }
@@ -793,9 +779,6 @@ __global__ __launch_bounds__(RB_THREADS, 1) void rowblock_kernel(RbParams p) {
             for (int j = 0; j < 6; ++j) {
                 const int r = wave * 6 + j;
                 const uint4 v = R1[r * 64 + (lane ^ (r & 15))];
-#ifdef RB_ABL_NOSTORE3
-                if (p.M < 0)
-#endif
                 *reinterpret_cast<uint4*>(p.out3 + srow(r) * ldo + pass * RB_C + 8 * lane) = v;
             }
         }

@@ -1,6 +1,6 @@
 """Times gvf_tile_sort_u64 (the per-tile half of the rasteriser's sort) on synthetic segments of one size each, depths uniform over a
-range as in the bench scene.  python scripts/bench_tile_sort.py [lib.so]  -- a second library (e.g. built with -DSORT_BUCKETS=0, the
-round-1 sorting networks) can be passed to compare."""
+range as in the bench scene.  python scripts/bench_tile_sort.py [lib.so]  -- a second library (e.g. a `_build --variant` build with another
+GVF_SORT_SMALL_N) can be passed to compare."""
 import ctypes, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

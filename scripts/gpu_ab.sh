@@ -4,7 +4,7 @@
 #   scripts/gpu_ab.sh <out-file> <reps> <leg> "<ENV settings of variant A>" "<ENV settings of variant B>" [...]
 #   leg: dit (ms_per_nfe) | raster (ms_per_step_serial + blend / preprocess / tile_sort stage ms) | live (ms_per_sample) | e2e (wall_ms + stages)
 # e.g.  scripts/gpu_ab.sh gpurun_out/r05/prefetch_ab.txt 3 dit "GVF_DIT_PREFETCH=1" "GVF_DIT_PREFETCH=0"
-# A variant may rebuild the library first:  "REBUILD='-DXT_PERSIST=0' ..."  is NOT supported here on purpose -- build the variants as
+# A variant may rebuild the library first:  "REBUILD='-DXT_RING_STAGES=4' ..."  is NOT supported here on purpose -- build the variants as
 # separate .so files before the call and select them with GVF_LIB=<path> (gvfdiffusion_amd/_lib.py).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"

@@ -13,7 +13,9 @@ for CTRS in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIV
             "GRBM_GUI_ACTIVE"; do
   i=$((i+1))
   rm -rf /tmp/pmc_${TAG}_$i
-  timeout 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d /tmp/pmc_${TAG}_$i -o p$i -- python "$REPO/$1" "${@:2}" > "$OUT/log$i.txt" 2>&1 < /dev/null
-  echo "pass $i rc=$?"
+  timeout -k 10 600 rocprofv3 --pmc $CTRS --kernel-trace --output-format csv -d /tmp/pmc_${TAG}_$i -o p$i -- python "$REPO/$1" "${@:2}" > "$OUT/log$i.txt" 2>&1 < /dev/null
+  RC=$?
+  echo "pass $i rc=$RC"
   for f in $(find /tmp/pmc_${TAG}_$i -name "*counter_collection.csv" 2>/dev/null); do cp "$f" "$OUT/pass$i.csv"; done
+  [ $RC -eq 0 ] || exit $RC                  # a failed pass ends the run: nothing more is started on the GPU
 done

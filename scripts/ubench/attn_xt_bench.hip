@@ -1,5 +1,5 @@
 // attn_xt_bench.hip -- standalone check + timing of csrc/attn_xt.hip (tiled-cache cross attention) on the DiT's shapes.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 <attn flags> [-DXT_PIPELINE=..] [-DXT_SUM_MFMA=..] attn_xt_bench.hip -o attn_xt_bench_<tag>
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 <attn flags> [-DXT_RING_STAGES=..] [-DXT_TILES_PER_STAGE=..] [-DXT_TIMING] attn_xt_bench.hip -o attn_xt_bench_<tag>
 // Checks sampled (frame, head, query) rows against a float64 host reference built from the SAME bf16 operands
 // (so the difference is the kernel's own arithmetic: bf16 probabilities, fp32 accumulation, bf16 output), then times it.
 #include "../../gvfdiffusion_amd/csrc/attn_xt.hip"

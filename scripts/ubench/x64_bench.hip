@@ -1,7 +1,7 @@
 // x64_bench.hip -- standalone check + timing of csrc/attn_xt64.hip (pre-tiled, LDS-resident K/V, head_dim 64) on the motion-VAE decoder's cross
 // attention: n Gaussians (queries shared by the T frames, inner stride 0) x L latents per frame, 12 heads of 64.  Same shapes, data and host
 // reference as kvres_bench.hip (csrc/attn.hip's kernel), so the two print comparable lines.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 <flags> [-DX64_ORDER=..] [-DX64_PASSES=..] x64_bench.hip -o x64_<tag>.bin
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 <flags> [-DX64_PASSES=..] x64_bench.hip -o x64_<tag>.bin
 //   x64_<tag>.bin [iters] [dtype 0 bf16 / 1 fp16] [n] [L] [gain] [force_exact]
 #include "../../gvfdiffusion_amd/csrc/attn_xt64.hip"
 #include <cmath>
@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
     const double us = ms * 1e3 / iters, tf = 4.0 * (double)T * n * L * C / us / 1e6;
     const double rel = sqrt(num / (den + 1e-300));
     int fb = 0; CK(hipMemcpy(&fb, dfb, 4, hipMemcpyDeviceToHost));
-    printf("vae decoder cross attention (tiled64) dt=%d n=%d L=%d gain=%.0f exact=%d order=%d passes=%d: rel_l2 %.3e max_abs %.3e nan %d fallback_waves %d | %8.1f us  %7.1f TFLOP/s (%.1f%% of 2.5 PF)\n",
-           dt, n, L, gain, force_exact, X64_ORDER, X64_PASSES, rel, maxabs, nan_count, fb, us, tf, tf / 25.0);
+    printf("vae decoder cross attention (tiled64) dt=%d n=%d L=%d gain=%.0f exact=%d passes=%d: rel_l2 %.3e max_abs %.3e nan %d fallback_waves %d | %8.1f us  %7.1f TFLOP/s (%.1f%% of 2.5 PF)\n",
+           dt, n, L, gain, force_exact, X64_PASSES, rel, maxabs, nan_count, fb, us, tf, tf / 25.0);
     return (rel < 1e-2 && nan_count == 0) ? 0 : 2;
 }

@@ -1,7 +1,7 @@
 """Bucket binning of the fused launch on a Morton-hostile sample -- needs an MI355X.
 
 The fused launch (preprocess_kernel<false>) stores its bin records at the Gaussians' own indices and bins them in index order when a frame's
-tiles fit the whole-frame table (rast.hip, GVF_BIN_ALGO), over Morton slots otherwise; the shared-activation launch keeps its Morton-slot
+tiles fit the whole-frame table (rast.hip, bin_index_kernel), over Morton slots otherwise; the shared-activation launch keeps its Morton-slot
 layout.  A spatially presorted sample and a random permutation of it must give the same instance counts per frame, and on each of them the
 fused path must give the shared path's bits (same per-tile key sets -> same sorted lists -> same images)."""
 import os
