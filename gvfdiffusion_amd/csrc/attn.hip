@@ -270,6 +270,13 @@ __device__ __forceinline__ float tile_first_max(const uint4* __restrict__ sKb, c
     return (m > -3.0e38f && m < 3.0e38f) ? m : 0.f;
 }
 
+// rows [r0, r1) of one (sequence, head)'s output set to +0 (a varlen sequence with no keys); 8-byte stores (o_sl % 4 == 0)
+template <int D>
+__device__ __forceinline__ void zero_rows(unsigned short* op, long long o_sl, int r0, int r1, int tid, int n_threads) {
+    for (int i = tid; i < (r1 - r0) * (D / 4); i += n_threads)
+        *reinterpret_cast<uint2*>(op + (long long)(r0 + i / (D / 4)) * o_sl + (i % (D / 4)) * 4) = make_uint2(0u, 0u);
+}
+
 // 8 operand-type values times a scalar, in fp32, one rounding
 template <int DT>
 __device__ __forceinline__ uint4 scale8(uint4 raw, float sc) {
@@ -306,7 +313,12 @@ __global__ __launch_bounds__(THREADS) void attn_fwd_kernel(AttnParams p) {
     if (p.cu_q != nullptr) {
         q_row0 = p.cu_q[outer]; Lq = p.cu_q[outer + 1] - (int)q_row0;
         k_row0 = p.cu_k[outer]; Lk = p.cu_k[outer + 1] - (int)k_row0;
-        if (qb * QB >= Lq || Lk <= 0) return;         // whole workgroup: uniform exit
+        if (qb * QB >= Lq) return;                    // whole workgroup: uniform exit
+        if (Lk <= 0) {                                // empty key range: this q-block's rows are zeros (flash-attn's varlen contract)
+            zero_rows<D>(p.out + outer * p.o_so + inner * p.o_si + head * p.o_sh + q_row0 * p.o_sl, p.o_sl, qb * QB,
+                         min(Lq, (qb + 1) * QB), tid, THREADS);
+            return;
+        }
     }
     const unsigned short* qp = p.q + outer * p.q_so + inner * p.q_si + head * p.q_sh + q_row0 * p.q_sl;
     const unsigned short* kp = p.k + outer * p.k_so + inner * p.k_si + head * p.k_sh + k_row0 * p.k_sl;
@@ -496,7 +508,13 @@ __global__ __launch_bounds__(RES_THREADS) void attn_kvres_kernel(AttnParams p, i
     if (p.cu_q != nullptr) {
         q_row0 = p.cu_q[outer]; Lq = p.cu_q[outer + 1] - (int)q_row0;
         k_row0 = p.cu_k[outer]; Lk = p.cu_k[outer + 1] - (int)k_row0;
-        if (qb * qt_per_wg * (RES_THREADS / 2) >= Lq || Lk <= 0) return;
+        const int r0 = qb * qt_per_wg * (RES_THREADS / 2);
+        if (r0 >= Lq) return;
+        if (Lk <= 0) {                                // empty key range: zeros, as attn_fwd_kernel
+            zero_rows<D>(p.out + outer * p.o_so + inner * p.o_si + head * p.o_sh + q_row0 * p.o_sl, p.o_sl, r0,
+                         min(Lq, r0 + qt_per_wg * (RES_THREADS / 2)), tid, RES_THREADS);
+            return;
+        }
     }
     const unsigned short* qp = p.q + outer * p.q_so + inner * p.q_si + head * p.q_sh + q_row0 * p.q_sl;
     const unsigned short* kp = p.k + outer * p.k_so + inner * p.k_si + head * p.k_sh + k_row0 * p.k_sl;

@@ -168,7 +168,11 @@ int gvf_attn_fwd_bf16(const void* q, const void* k, const void* v, void* out,
 /* Variable-length batch over packed token lists (the reference's sparse attention seam,
  * model/sparse_attention/full_attn.py:189-210: flash_attn_varlen_* / xformers BlockDiagonalMask): sequence s
  * owns query rows [cu_seqlens_q[s], cu_seqlens_q[s+1]) and key rows [cu_seqlens_k[s], cu_seqlens_k[s+1]) of
- * the packed tensors; strides as above with strides[0] (outer) normally 0.  cu_seqlens: device int32 [n_seqs+1]. */
+ * the packed tensors; strides as above with strides[0] (outer) normally 0.  cu_seqlens: device int32 [n_seqs+1].
+ * A sequence with no keys (cu_seqlens_k[s+1] == cu_seqlens_k[s]) and Lq > 0 query rows gets zero output rows, as
+ * flash-attn's varlen kernel writes for an empty key range; a sequence with no queries writes nothing.
+ * max_Lq / max_Lk must be >= every sequence's Lq / Lk (they size the grid and, for the K/V-resident kernel, its LDS):
+ * smaller values are outside the contract and are not checked on the device. */
 int gvf_attn_varlen_fwd(int dtype, const void* q, const void* k, const void* v, void* out, int n_seqs,
                         const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k, int max_Lq, int max_Lk,
                         int H, int head_dim,
