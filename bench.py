@@ -10,7 +10,9 @@ configs[1]) through the fused batched rasteriser (gvf_rast_forward_batched).  In
 HBM when the timed region starts.  With N > 1 each rank renders its own sample (batch sharded over
 the GPUs, weak scaling) and the ranks exchange the finished uint8 frames with ONE all-gather per
 step (RCCL), overlapped with the next step's rendering on a side stream.
-rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline`.
+rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figure; --full adds
+the serial instrumented pass (stage times, `roofline`), the secondary workloads (differentiable render, DiT, end to end, live render,
+sharded sampling) and the CPU baselines.
 """
 import argparse
 import ctypes
@@ -39,8 +41,10 @@ def parse():
     ap.add_argument("--res", type=int, default=800)
     ap.add_argument("--frames", type=int, default=24)
     ap.add_argument("--sh-degree", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dit", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the serial instrumented pass (stage times, roofline), the secondary workloads and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-dit", action="store_true", help="with --full: skip the secondary workloads")
     ap.add_argument("--e2e-only", action="store_true", help="profiling aid: run only the end-to-end leg and print its object")
     ap.add_argument("--dit-only", action="store_true", help="profiling aid: run only the DiT leg and print its object")
     ap.add_argument("--live-only", action="store_true", help="profiling aid: run only the live-render leg (32 x 128 x 512^2) and print its object")
@@ -836,22 +840,23 @@ def main():
     if every_step:
         for e in consumed:
             e.record()
-    # ---- pass 1: serial and instrumented (per-stage HIP events inside the library): stage times, roofline, single-stream step time
-    for i in range(a.warmup):
-        step(i, 1)
-    final_gather(1, max(a.warmup, 1))               # first all-gather of the process: RCCL sets its channels up here, outside any timed region
-    barrier()
-    _lib.check(_lib.lib().gvf_rast_profile_enable(1), "profile_enable")
-    t0 = time.perf_counter()
-    for i in range(a.steps):
-        step(i, 1)
-    final_gather(1, a.steps)
-    barrier()
-    dt_serial = time.perf_counter() - t0
-    ms = (ctypes.c_float * len(STAGES))()
-    calls = ctypes.c_int(0)
-    _lib.check(_lib.lib().gvf_rast_profile_read(ms, ctypes.byref(calls)), "profile_read")
-    _lib.lib().gvf_rast_profile_enable(0)
+    # ---- pass 1 (--full): serial and instrumented (per-stage HIP events inside the library): stage times, roofline, single-stream step time
+    if a.full:
+        for i in range(a.warmup):
+            step(i, 1)
+        final_gather(1, max(a.warmup, 1))           # first all-gather of the process: RCCL sets its channels up here, outside any timed region
+        barrier()
+        _lib.check(_lib.lib().gvf_rast_profile_enable(1), "profile_enable")
+        t0 = time.perf_counter()
+        for i in range(a.steps):
+            step(i, 1)
+        final_gather(1, a.steps)
+        barrier()
+        dt_serial = time.perf_counter() - t0
+        ms = (ctypes.c_float * len(STAGES))()
+        calls = ctypes.c_int(0)
+        _lib.check(_lib.lib().gvf_rast_profile_read(ms, ctypes.byref(calls)), "profile_read")
+        _lib.lib().gvf_rast_profile_enable(0)
     # ---- pass 2: the timed K steps, n_slots samples in flight (every slot warmed at least twice, whatever W is)
     serial_frames = []
     for k in range(n_slots):                    # what each slot's sample looks like rendered alone, on one stream
@@ -883,7 +888,7 @@ def main():
         k = (a.steps - 1) % n_slots
         dump_outputs(a.dump_outputs, slots[k].color, slots[k].nr)
 
-    t = torch.tensor([dt, dt_serial], dtype=torch.float64, device=dev if (not multi or dist.get_backend() == "nccl") else "cpu")
+    t = torch.tensor([dt, dt_serial if a.full else 0.0], dtype=torch.float64, device=dev if (not multi or dist.get_backend() == "nccl") else "cpu")
     if multi:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt, dt_serial = float(t[0].item()), float(t[1].item())
@@ -892,20 +897,12 @@ def main():
     assert all(int(w_.nr.to(torch.int64).sum()) <= w_.cap for w_ in slots), "workspace overflow during the timed region"
 
     if rank == 0:
-        traffic, traffic_note = pmc_traffic("blend_kernel", a, S, F)
-        valu_issue = pmc_valu_issue("blend_kernel", a, S, F)
-        ncalls = max(1, calls.value)
-        stage_ms = {s: ms[k] / ncalls for k, s in enumerate(STAGES)}
-        blend_s = stage_ms["blend"] * 1e-3
-        achieved = work.alg_bytes_blend_launch() / blend_s / 1e9 if blend_s > 0 else 0.0
-        gpu_frame_s = sum(stage_ms.values()) * 1e-3 / F
         out = {
             "metric": "4D frames/sec (800x800x24f, 256k Gaussians) + DiT denoise steps/sec",
             "value": round(world * F * a.steps / dt, 2),
             "unit": "frames/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(dt / a.steps * 1e3, 4),
-            "ms_per_step_serial": round(dt_serial / a.steps * 1e3, 4),       # one sample at a time on one stream (with the stage events)
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": "BASELINE configs[1]: single-GPU HIP rasteriser, one 4D sample per step = "
@@ -915,48 +912,59 @@ def main():
                        "instances_per_frame": round(work.D / F, 1), "instances_binned_per_frame": round(work.D_binned / F, 1), "parallelism": f"sample-sharded x{world}",
                        "samples_in_flight": n_slots,
                        "pipelining": f"{n_slots} DIFFERENT samples in flight per GPU (own Gaussians, deltas, HIP stream, workspace and frame buffer "
-                                     "each; every slot's frames are asserted bit-identical to its serial render); stage_ms_per_step, roofline and "
-                                     "ms_per_step_serial are from a serial instrumented pass over the same steps",
+                                     "each; every slot's frames are asserted bit-identical to its serial render); with --full, stage_ms_per_step, roofline "
+                                     "and ms_per_step_serial come from a serial instrumented pass over the same steps",
                        "collective": None if not multi else (
                            "every counted sample is collected inside the timed region: uint8 conversion + one all_gather_into_tensor per step "
                            f"({world} x {F * 3 * S * S / 1e6:.0f} MB) on a side stream, overlapped with the next step's rendering" if every_step else
                            "RENDER-ONLY timing (GVF_BENCH_GATHER_EVERY_STEP=0): only the LAST step's frames are gathered (once, at the end of the "
                            "timed region); the other steps' frames are counted but not collected")},
-            "roofline": {"bound": "hbm", "kernel": "blend_kernel (R6, one launch = all frames of the step)",
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                         "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload (scripts/gpu_pmc.sh, "
-                                           "scripts/pmc_summary.py; FETCH x2 gfx950 correction), bytes per launch, from the committed "
-                                           "summary stamped with the rasteriser source hash: " + traffic_note,
-                         # the same launch priced on the instances the kernel actually touches (alpha-box culled binning), 36 B each
-                         "frac_on_binned_instances": round((work.D_binned * 36 + F * S * S * 12) / blend_s / 1e9 / HBM_PEAK_GBS, 5) if blend_s > 0 else 0,
-                         "valu_issue": valu_issue,
-                         # The bound that actually binds this launch: the compositing loop is 16 vector instructions per list
-                         # entry of which one is a v_exp_f32; on the `valu_issue` scale (SQ_ACTIVE_INST_VALU x 2 cycles / busy cycles) that mix
-                         # topped out at ~0.69 with the loop of rounds 5-6 (profiles/r05_blend_phase_stamps.txt) and at ~0.73 with the lane-mask form of
-                         # its predicates (the loop-only figure 41.4 -> 38.9 ticks per entry per SIMD, same 16 vector instructions:
-                         # profiles/r06_ubench_blend_step.txt); `achieved` = the counter figure of the committed SQ pass.
-                         # The one restructuring not priced before round 6 -- exponents from six v_mfma_f32_4x4x1 per 4 splats, 11 vector
-                         # instructions per entry -- is 8 % SLOWER in a loop-only micro-benchmark (profiles/r06_ubench_blend_step.txt), so the
-                         # kernel stays and this is its roofline; the HBM figure above is what north_star asked to see.
-                         "binding_bound": None if not valu_issue else {
-                             "bound": "valu", "unit": "fraction of VALU issue cycles", "achieved": valu_issue.get("valu_issue"), "peak": 0.73,
-                             "frac": round(valu_issue.get("valu_issue", 0.0) / 0.73, 4),
-                             "source": valu_issue.get("source")},
-                         # BASELINE's north star prices "tile-sort + blend" together: the per-tile sort moves 8 B in + 4 B out per binned
-                         # instance (PMC: 0.25 GB per launch = exactly that), priced like the blend on upstream's instance count
-                         "tile_sort_plus_blend": (lambda b_, t_: {"alg_bytes": int(b_), "ms": round(t_ * 1e3, 4), "achieved_GBs": round(b_ / t_ / 1e9, 2),
-                                                                  "frac": round(b_ / t_ / 1e9 / HBM_PEAK_GBS, 5)})(
-                             work.alg_bytes_blend_launch() + 12.0 * work.D, (stage_ms["blend"] + stage_ms["tile_sort"]) * 1e-3)
-                         if stage_ms["blend"] + stage_ms["tile_sort"] > 0 else None,
-                         "alg_bytes_per_launch": int(work.alg_bytes_blend_launch()),
-                         "avg_launch_ms": round(stage_ms["blend"], 4)},
-            "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
-            "pipeline_roofline": {"alg_bytes_per_frame": int(work.alg_bytes_frame()),
-                                  "achieved_GBs": round(work.alg_bytes_frame() / gpu_frame_s / 1e9, 2) if gpu_frame_s else 0,
-                                  "frac": round(work.alg_bytes_frame() / gpu_frame_s / 1e9 / HBM_PEAK_GBS, 5) if gpu_frame_s else 0},
         }
-        if not multi and not a.no_dit:
+        if a.full:
+            traffic, traffic_note = pmc_traffic("blend_kernel", a, S, F)
+            valu_issue = pmc_valu_issue("blend_kernel", a, S, F)
+            ncalls = max(1, calls.value)
+            stage_ms = {s: ms[k] / ncalls for k, s in enumerate(STAGES)}
+            blend_s = stage_ms["blend"] * 1e-3
+            achieved = work.alg_bytes_blend_launch() / blend_s / 1e9 if blend_s > 0 else 0.0
+            gpu_frame_s = sum(stage_ms.values()) * 1e-3 / F
+            out.update({
+                "ms_per_step_serial": round(dt_serial / a.steps * 1e3, 4),       # one sample at a time on one stream (with the stage events)
+                "roofline": {"bound": "hbm", "kernel": "blend_kernel (R6, one launch = all frames of the step)",
+                             "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                             "traffic_source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this workload (scripts/gpu_pmc.sh, "
+                                               "scripts/pmc_summary.py; FETCH x2 gfx950 correction), bytes per launch, from the committed "
+                                               "summary stamped with the rasteriser source hash: " + traffic_note,
+                             # the same launch priced on the instances the kernel actually touches (alpha-box culled binning), 36 B each
+                             "frac_on_binned_instances": round((work.D_binned * 36 + F * S * S * 12) / blend_s / 1e9 / HBM_PEAK_GBS, 5) if blend_s > 0 else 0,
+                             "valu_issue": valu_issue,
+                             # The bound that actually binds this launch: the compositing loop is 16 vector instructions per list
+                             # entry of which one is a v_exp_f32; on the `valu_issue` scale (SQ_ACTIVE_INST_VALU x 2 cycles / busy cycles) that mix
+                             # topped out at ~0.69 with the loop of rounds 5-6 (profiles/r05_blend_phase_stamps.txt) and at ~0.73 with the lane-mask form of
+                             # its predicates (the loop-only figure 41.4 -> 38.9 ticks per entry per SIMD, same 16 vector instructions:
+                             # profiles/r06_ubench_blend_step.txt); `achieved` = the counter figure of the committed SQ pass.
+                             # The one restructuring not priced before round 6 -- exponents from six v_mfma_f32_4x4x1 per 4 splats, 11 vector
+                             # instructions per entry -- is 8 % SLOWER in a loop-only micro-benchmark (profiles/r06_ubench_blend_step.txt), so the
+                             # kernel stays and this is its roofline; the HBM figure above is what north_star asked to see.
+                             "binding_bound": None if not valu_issue else {
+                                 "bound": "valu", "unit": "fraction of VALU issue cycles", "achieved": valu_issue.get("valu_issue"), "peak": 0.73,
+                                 "frac": round(valu_issue.get("valu_issue", 0.0) / 0.73, 4),
+                                 "source": valu_issue.get("source")},
+                             # BASELINE's north star prices "tile-sort + blend" together: the per-tile sort moves 8 B in + 4 B out per binned
+                             # instance (PMC: 0.25 GB per launch = exactly that), priced like the blend on upstream's instance count
+                             "tile_sort_plus_blend": (lambda b_, t_: {"alg_bytes": int(b_), "ms": round(t_ * 1e3, 4), "achieved_GBs": round(b_ / t_ / 1e9, 2),
+                                                                      "frac": round(b_ / t_ / 1e9 / HBM_PEAK_GBS, 5)})(
+                                 work.alg_bytes_blend_launch() + 12.0 * work.D, (stage_ms["blend"] + stage_ms["tile_sort"]) * 1e-3)
+                             if stage_ms["blend"] + stage_ms["tile_sort"] > 0 else None,
+                             "alg_bytes_per_launch": int(work.alg_bytes_blend_launch()),
+                             "avg_launch_ms": round(stage_ms["blend"], 4)},
+                "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
+                "pipeline_roofline": {"alg_bytes_per_frame": int(work.alg_bytes_frame()),
+                                      "achieved_GBs": round(work.alg_bytes_frame() / gpu_frame_s / 1e9, 2) if gpu_frame_s else 0,
+                                      "frac": round(work.alg_bytes_frame() / gpu_frame_s / 1e9 / HBM_PEAK_GBS, 5) if gpu_frame_s else 0},
+            })
+        if a.full and not multi and not a.no_dit:
             for w_ in slots:
                 w_.__dict__.pop("ws", None)
             torch.cuda.empty_cache()
@@ -985,15 +993,15 @@ def main():
                 sh["serial_B1_equivalent"] = {"wall_ms": round(ser_ms, 2), "denoise_steps_per_s": round(sh["samples"] * 32 / ser_ms * 1e3, 2),
                                               "speedup_of_this_line": round(ser_ms / sh["wall_ms"], 4)}
                 out["sharded_sampling"] = sh
-        if multi and not a.no_dit:
+        if a.full and multi and not a.no_dit:
             for w_ in slots:
                 w_.__dict__.pop("ws", None)
             torch.cuda.empty_cache()
-        if not multi and not a.no_cpu_baseline:
+        if a.full and not multi and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(work)
             if "dit" in out:
                 out["dit"]["cpu_baseline"] = dit_cpu_baseline()
-    if multi and not a.no_dit:
+    if a.full and multi and not a.no_dit:
         # every rank takes part; rank 0 prints (the driver reads ONE JSON line)
         if rank != 0:
             for w_ in slots:

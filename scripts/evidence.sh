@@ -45,7 +45,7 @@ if has vae; then
   done
   timeout -k 10 900 python scripts/bench_gemm_vae.py 2>&1 | { grep -v amdgpu.ids || true; } > $O/gemm_vae_shapes.txt || fail "GEMM shapes" $?
 fi
-if has bench; then timeout -k 10 1800 python bench.py 2>$O/bench_err.log | tail -1 > $O/bench_line.json || fail bench.py $?; fi
+if has bench; then timeout -k 10 1800 python bench.py --full 2>$O/bench_err.log | tail -1 > $O/bench_line.json || fail bench.py $?; fi
 if has smoke; then timeout -k 10 900 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || fail smoke $?; fi
 if has tests; then timeout -k 10 2400 python -m pytest tests -m gpu -q 2>&1 | tail -8 > $O/pytest_gpu.txt || fail "GPU tests" $?; fi
 rm -rf gpurun_out/pmc_${TAG}_*/pass*.csv gpurun_out/prof_$TAG/*kernel_trace.csv

@@ -13,7 +13,7 @@ mkdir -p "$(dirname "$OUT")"
 export GVF_BENCH_DIT_CFG3=0 GVF_BENCH_DIT_INFLIGHT=0 GVF_BENCH_DIT_OTHER_DTYPE=0 GVF_BENCH_DIT_HOSTILE=${GVF_BENCH_DIT_HOSTILE:-0}
 case $LEG in
   dit)    ARGS="--dit-only --no-cpu-baseline"; PY="print(d['ms_per_nfe'], d['value'], d.get('softmax_guard'))" ;;
-  raster) ARGS="--no-dit --no-cpu-baseline --streams 1"; PY="s=d['stage_ms_per_step']; print(d['ms_per_step_serial'], s['blend'], s['preprocess'], s['tile_sort'], d['value'])" ;;
+  raster) ARGS="--full --no-dit --no-cpu-baseline --streams 1"; PY="s=d['stage_ms_per_step']; print(d['ms_per_step_serial'], s['blend'], s['preprocess'], s['tile_sort'], d['value'])" ;;
   live)   ARGS="--live-only"; PY="print(d['ms_per_sample'], d['value'])" ;;
   e2e)    ARGS="--e2e-only"; PY="print(d['wall_ms'], d['stage_ms'], d['nfe'])" ;;
   *) echo "unknown leg $LEG"; exit 2 ;;

@@ -23,7 +23,7 @@ if 'sharded_sampling' in d: print('sharded', json.dumps(d['sharded_sampling'])[:
 case $CASE in
   first)    # shared activation arithmetic: raster + sampler GPU tests with per-test durations, then the whole bench line (new anchor / parity fields)
     timeout 900 python -m pytest tests/test_rast_gpu.py tests/test_sampler.py tests/test_render_driver_gpu.py tests/test_pipeline_gpu.py -m gpu -q --durations=30 -x > $O/pytest.txt 2>&1; echo "pytest rc=$?"; tail -45 $O/pytest.txt
-    timeout 900 python bench.py 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json; tail -5 $O/bench_err.log ;;
+    timeout 900 python bench.py --full 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json; tail -5 $O/bench_err.log ;;
   suite)    # the whole GPU suite with durations
     timeout 1500 python -m pytest tests -m gpu -q --durations=40 > $O/pytest.txt 2>&1; echo "pytest rc=$?"; tail -60 $O/pytest.txt ;;
   batch)    # where does a batched forward spend its time?  kernel traces of the DiT leg at B = 1, 3, 8 (one forward covers B samples) + the GPU suite's durations
@@ -47,15 +47,15 @@ case $CASE in
     timeout 900 python -m pytest tests/test_sampler.py tests/test_vae_gpu.py tests/test_sparse_vae_gpu.py tests/test_dit_gpu.py -m gpu -q --durations=12 -x > $O/pytest.txt 2>&1; echo "pytest rc=$?"; tail -22 $O/pytest.txt ;;
   second)   # the fixed blend-step micro-benchmark, the bench line with the three sharded modes, and the tests touched since (durations with the oracle disk cache)
     scripts/ubench/blend_step.bin > $O/ubench_blend_step.txt 2>&1; cat $O/ubench_blend_step.txt
-    timeout 900 python bench.py 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json; tail -3 $O/bench_err.log
+    timeout 900 python bench.py --full 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json; tail -3 $O/bench_err.log
     rm -rf /tmp/gvf_oracle_cache
     timeout 1200 python -m pytest tests/test_sampler.py tests/test_dit_gpu.py tests/test_vae_gpu.py tests/test_sparse_vae_gpu.py tests/test_distributed.py -m gpu -q --durations=12 > $O/pytest.txt 2>&1; echo "pytest rc=$?"; tail -22 $O/pytest.txt ;;
   clocks)   # is the batched forward clock / power limited?  + the sampler test on the device after the tolerance fix
     python scripts/dit_clock_probe.py 5 2>&1 | grep -v amdgpu.ids > $O/dit_clock_probe.txt; cat $O/dit_clock_probe.txt
     timeout 600 python -m pytest tests/test_sampler.py -m gpu -q > $O/pytest.txt 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.txt ;;
   streams)  # raster samples in flight 1..4 (the headline's `value`), the three sharded modes with the full-length warm-up, sampler test
-    for n in 2 3 4 2 3; do echo -n "streams $n: "; python bench.py --no-dit --no-cpu-baseline --streams $n 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['ms_per_step_serial'])"; done | tee $O/raster_streams.txt
-    GVF_BENCH_DIT_CFG3=0 GVF_BENCH_DIT_INFLIGHT=0 GVF_BENCH_DIT_OTHER_DTYPE=0 GVF_BENCH_DIT_HOSTILE=0 timeout 900 python bench.py --steps 5 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json
+    for n in 2 3 4 2 3; do echo -n "streams $n: "; python bench.py --full --no-dit --no-cpu-baseline --streams $n 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['ms_per_step_serial'])"; done | tee $O/raster_streams.txt
+    GVF_BENCH_DIT_CFG3=0 GVF_BENCH_DIT_INFLIGHT=0 GVF_BENCH_DIT_OTHER_DTYPE=0 GVF_BENCH_DIT_HOSTILE=0 timeout 900 python bench.py --full --steps 5 2>$O/bench_err.log | tail -1 > $O/bench_line.json; bench_summary $O/bench_line.json
     timeout 600 python -m pytest tests/test_sampler.py -m gpu -q -s 2>&1 | tail -6 ;;
   rbfill)   # VERDICT r5 item 2a priced by ablation: the row-block launches with 3 / 2 of a wave's 4 column tiles refilled per k-step = the weight traffic
             # 64-row / 96-row workgroups would leave (timing only: the results are wrong), at batch 3 and batch 1

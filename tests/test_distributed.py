@@ -187,7 +187,7 @@ def test_two_rank_sharded_sampling_equals_single_process(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_n2_line_carries_the_multi_rank_record(tmp_path):
-    """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one process per rank), on the one-GPU box: the two ranks share
+    """`bench.py --full --gpus 2` launched as the driver launches it (torch.distributed.run, one process per rank), on the one-GPU box: the two ranks share
     the GPU and talk over gloo (GVF_BENCH_BACKEND=gloo, a test aid of bench.py; RCCL needs one GPU per rank), reduced raster size, the full
     DiT / VAE sharded-sampling leg.  A FUNCTIONAL record of the N > 1 code path -- the per-step frame gather inside the timed region, the
     batch-sharded sampling of BASELINE configs[4], the max-over-ranks reductions -- not a performance figure: the line must say who took part
@@ -196,7 +196,7 @@ def test_bench_n2_line_carries_the_multi_rank_record(tmp_path):
     import subprocess
     env = dict(os.environ, GVF_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
-           str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--gaussians", "32768", "--res", "256"]
+           str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--gaussians", "32768", "--res", "256"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
