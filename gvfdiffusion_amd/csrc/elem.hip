@@ -477,6 +477,10 @@ extern "C" int gvf_layernorm_modulate(int dtype, const float* x, void* out_bf16,
         return GVF_EINVAL;
     if (scale != nullptr && (rows_per_group <= 0 || ((C % 256) == 0 && (mod_ld % 4) != 0))) return GVF_EINVAL;
     if ((((uintptr_t)x) & 15) || (((uintptr_t)out_bf16) & 7)) return GVF_EINVAL;
+    // the float4 kernel loads ln_w, ln_b, shift and scale 16 bytes at a time (mod_ld % 4 == 0 keeps every group's row aligned with the first)
+    if ((C % 256) == 0 && C <= 1024 &&
+        ((((uintptr_t)ln_w) & 15) || (((uintptr_t)ln_b) & 15) || (((uintptr_t)shift) & 15) || (((uintptr_t)scale) & 15)))
+        return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     const int rpg = rows_per_group > 0 ? rows_per_group : 1;

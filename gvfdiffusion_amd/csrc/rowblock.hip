@@ -903,6 +903,8 @@ static int rowblock_launch(const gvf_rowblock_args* a, int dtype, void* stream_)
         return GVF_EINVAL;
     if (a->N3 == 0 && a->hb_out == nullptr && a->hidden == 0) return GVF_EINVAL;       // nothing would consume the LayerNorm (with the MLP: the
                                                                                         // stream update alone is a result; LayerNorm ln2 is skipped)
+    if (a->K1 == 0 && a->hidden == 0 && a->N3 == 0) return GVF_EINVAL;                  // LayerNorm alone: the weight stream would be empty, and the
+                                                                                        // kernel's prefetch always reads a step of it
     if ((a->k_tiles == nullptr) != (a->v_tiles == nullptr)) return GVF_EINVAL;
     if (a->k_tiles != nullptr && (a->N3 != 3 * RB_C || a->kv_L <= 0 || a->kv_L % 64 != 0 || !(a->k_scale > 0.f) ||
                                   (((uintptr_t)a->k_tiles) & 15) || (((uintptr_t)a->v_tiles) & 15)))

@@ -93,6 +93,7 @@ int gvf_gemm_ln_bf16(const float* X, int ldx, const float* row_stats, int n_part
  *   W3:  gvf_rowblock_pack_weight                                            -- only when N3 != 0.
  * K1 = 0 skips the closing projection (x already holds the sub-layer's result; `a`, b1, gate1 NULL, no W1 segment in `w`).  With the MLP and
  * neither N3 nor hb_out the launch ends after the MLP's update of x (LayerNorm ln2 is skipped: final_layer reads the stream itself).
+ * A launch needs at least one weight segment: K1 = 0 with neither the MLP nor N3 (LayerNorm alone) is GVF_EINVAL -- use gvf_layernorm_modulate.
  * K1 (<= 512, multiple of 128) is the PADDED depth of W1; A is bf16 [M][lda] with lda >= K1.  gate / shift / scale: f32, row g =
  * row / rows_per_group of leading dimension mod_ld (rows_per_group a multiple of 48); NULL = no gate / no modulate.
  * Rounding points are those of the unfused launches: bf16 operands, fp32 accumulation, fp32 stream, LayerNorm in fp32,
@@ -307,7 +308,9 @@ int gvf_attn_fold_reduce(const float* part, const float* bias, float* out, int n
 
 /* out_bf16[r][:] = LN(x[r][:]) (eps, no affine) then either  * ln_w + ln_b  (affine LayerNorm, norm3/4)
  * or  * (1 + scale[g]) + shift[g]  (adaLN, g = r / rows_per_group; shift/scale rows have stride mod_ld),
- * x f32 [rows][C]; C a multiple of 256 (<= 1024) takes the register-resident fast path. */
+ * x f32 [rows][C]; C a multiple of 256 (<= 1024) takes the register-resident fast path, which loads the four vectors 16 bytes at a
+ * time: there ln_w, ln_b, shift and scale must be 16-byte aligned (and mod_ld a multiple of 4), else GVF_EINVAL -- they are not routed
+ * to the generic kernel, so that a misaligned view is noticed instead of silently costing the slow path. */
 int gvf_layernorm_modulate(int dtype, const float* x, void* out16, int rows, int C, float eps,
                            const float* ln_w, const float* ln_b,
                            const float* shift, const float* scale, int mod_ld, int rows_per_group,
