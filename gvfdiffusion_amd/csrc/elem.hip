@@ -176,7 +176,8 @@ __global__ __launch_bounds__(256) void split3_bf16_kernel(const float* __restric
 __device__ __forceinline__ float bf2f_(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
 
 // dot products of 8 weight rows (o0 + 16 u) with the LDS vector v[0, K): all 8 rows' loads in flight together (one output at a time
-// the kernel is a chain of ~2 us memory latencies: 0.5 ms)
+// the kernel is a chain of ~2 us memory latencies: 0.5 ms).  K is the true width: the last group of 4 is loaded whole (ldw is a multiple
+// of 4) and the columns from K on are masked to +0, so what the caller keeps in the weights' padding never reaches the sum.
 __device__ __forceinline__ void te_dot8(const unsigned short* __restrict__ W, int ldw, int o0, int n_out, int K, const float* v, int lane, float (&acc)[8]) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc[u] = 0.f;
@@ -186,6 +187,12 @@ __device__ __forceinline__ void te_dot8(const unsigned short* __restrict__ W, in
         for (int u = 0; u < 8; ++u) {
             const int o = o0 + 16 * u;
             w[u] = o < n_out ? *reinterpret_cast<const uint2*>(W + (size_t)o * ldw + k) : make_uint2(0u, 0u);
+        }
+        if (k + 4 > K) {                                     // the row's last, partial group: K - k = 1, 2 or 3 columns are real
+            const int n = K - k;
+            const unsigned mx = n >= 2 ? 0xffffffffu : 0x0000ffffu, my = n >= 3 ? 0x0000ffffu : 0u;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { w[u].x &= mx; w[u].y &= my; }
         }
         const float4 x = *reinterpret_cast<const float4*>(v + k);
 #pragma unroll
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(1024) void timestep_embed_kernel(const float* __res
     __syncthreads();
     float acc[8];
     for (int o0 = wave; o0 < C; o0 += 128) {                 // 16 waves x 8 rows per round
-        te_dot8(W0, ldw0, o0, C, (F + 3) & ~3, sA, lane, acc);
+        te_dot8(W0, ldw0, o0, C, F, sA, lane, acc);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int o = o0 + 16 * u;
@@ -231,7 +238,7 @@ __global__ __launch_bounds__(1024) void timestep_embed_kernel(const float* __res
     // one CU pulls ~70 GB/s, so one workgroup alone would spend 13 us on the 0.75 MB of weights)
     const int per = (C + gridDim.y - 1) / gridDim.y, lo = blockIdx.y * per, hi = lo + per < C ? lo + per : C;
     for (int o0 = lo + wave; o0 < hi; o0 += 128) {
-        te_dot8(W2, ldw2, o0, hi, (C + 3) & ~3, sB, lane, acc);
+        te_dot8(W2, ldw2, o0, hi, C, sB, lane, acc);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int o = o0 + 16 * u;

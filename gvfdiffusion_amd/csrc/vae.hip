@@ -220,6 +220,8 @@ extern "C" int gvf_vae_embed(int dtype, const float* queries, int qdim, const fl
                              void* stream_) {
     if (dtype != GVF_DT_BF16 && dtype != GVF_DT_F16) return GVF_EINVAL;
     if (P < 0 || qdim < 3 || qdim > QE_MAXQ || C <= 0 || C > 64 * QE_MAXI || (C % 6) != 0) return GVF_EINVAL;
+    // the LDS kernel keeps W (pitch qdim | 1), the bias and omega in dynamic LDS: at most the 64 KiB a plain launch may ask for
+    if (((size_t)C * (qdim | 1) + C + C / 6) * sizeof(float) > 65536) return GVF_EINVAL;
     if (P == 0) return GVF_OK;
     if (!queries || !W || !bias || !omega || !out_bf16) return GVF_EINVAL;
     (void)hipGetLastError();

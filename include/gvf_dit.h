@@ -344,7 +344,12 @@ int gvf_split3_bf16(const float* src, int64_t ld_src, void* dst, int64_t rows, i
  *                               (w_t = the weight TRANSPOSED, f32 [Cin][C])
  *                               (model/dit.py:455-460: input_layer(x) + the position embedding broadcast over the frames; pos may be NULL)
  *   gvf_dit_final_layer_f32:    out[row] = w (LayerNorm(x[row]) * (1 + scale[g]) + shift[g]) + bias              (model/dit.py:298-303)
- * Weights are the nn.Linear fp32 weights as stored ([out][in], contiguous).  C <= 512 (a multiple of 4) for the last two; Cin <= 24; Cout <= 32. */
+ * Weights are the nn.Linear fp32 weights as stored ([out][in], contiguous).  Domains (anything else is GVF_EINVAL, nothing launched):
+ *   timestep_embed_f32: freq_dim and C multiples of 4, <= 1024; max_period > 1; w0, w2 16-byte aligned;
+ *   modulation_f32:     C a multiple of 4, <= 1024; N >= 1; w 16-byte aligned;
+ *   input_layer_f32:    Cin <= 24; C <= 512 (any); with pos: pos_period >= 1 and rows_per_group a positive multiple of it;
+ *   final_layer_f32:    C <= 512, a multiple of 4; Cout <= 32; x, w 16-byte aligned; shift and scale both or neither, and with them
+ *                       rows_per_group >= 1, mod_ld a multiple of 4, shift / scale 16-byte aligned. */
 int gvf_dit_timestep_embed_f32(const float* t, int B, int freq_dim, float max_period, const float* w0, const float* b0, const float* w2,
                                const float* b2, int C, float* out_silu, float* t_emb, void* stream);
 int gvf_dit_modulation_f32(const float* s, int B, int C, const float* w, const float* bias, int N, float* out, void* stream);
@@ -357,7 +362,9 @@ int gvf_dit_final_layer_f32(const float* x, int M, int C, float eps, const float
  *   t_freq = [cos(t f_i) | sin(t f_i)], f_i = max_period^(-i / (freq_dim/2));  t_emb = W2 silu(W0 t_freq + b0) + b2;
  *   out[b][0..C) = bf16(silu(t_emb[b])), zero-padded to ld_out columns -- the A operand of the GEMM that computes every block's
  * modulation vectors.  t: f32 [B]; w0: bf16 [C][ldw0 >= freq_dim], w2: bf16 [C][ldw2 >= C] (nn.Linear layout); t_emb: optional f32
- * [B][C] copy of the embedding.  freq_dim even, <= 1024; C <= 1024.  Operands are rounded to bf16 where the unfused launches
+ * [B][C] copy of the embedding.  freq_dim even, <= 1024; C <= 1024; ldw0 >= freq_dim and ldw2 >= C, both rounded up to a multiple
+ * of 4, and themselves multiples of 4; w0 / w2 8-byte aligned; max_period > 1; ld_out >= C.  The weights' padding columns (freq_dim ..
+ * ldw0, C .. ldw2) are loaded but masked: they may hold anything, NaN included.  Operands are rounded to bf16 where the unfused launches
  * (gvf_cast_pad_bf16 + gvf_gemm_bf16) round them. */
 int gvf_dit_timestep_embed_bf16(const float* t, int B, int freq_dim, float max_period, const void* w0_bf16, int ldw0, const float* b0,
                                 const void* w2_bf16, int ldw2, const float* b2, int C, void* out_bf16, int ld_out, float* t_emb,

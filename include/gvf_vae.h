@@ -29,7 +29,10 @@ int gvf_geglu_bf16(const void* in_bf16, int ld_in, void* out_bf16, int ld_out, i
 /* out bf16 [P][C] = LN_pre( LN_emb(q W^T + b) + LN_emb(point_embed(q[:, :3])) ), LayerNorms without affine; the two
  * embedding norms use eps_embed (nn.LayerNorm default 1e-5, :393-394), the PreNorm one eps_prenorm (1e-6, :77):
  * queries f32 [P][qdim] (qdim >= 3, <= 16), W f32 [C][qdim], bias f32 [C], omega f32 [C/6];
- * point_embed(p) = concat over axis a of [sin(p_a * omega), cos(p_a * omega)].  C % 6 == 0, C <= 1024.
+ * point_embed(p) = concat over axis a of [sin(p_a * omega), cos(p_a * omega)].  C % 6 == 0, C <= 1024, and
+ * (C * (qdim | 1) + C + C / 6) * 4 <= 65536 (the weights, bias and omega of a workgroup in LDS: C <= 1008 at qdim 14 / 15, C <= 900 at
+ * qdim 16); anything else is GVF_EINVAL and nothing is launched.  Positions q[:, :3] in [-0.5, 0.5], omega <= 1: the phases are
+ * evaluated by the hardware sine / cosine, 1e-6 absolute for |phase| <= 0.5 rad.
  * All arithmetic fp32 (the reference's autocast would round the 14 -> C Linear to bf16). */
 int gvf_vae_query_embed_bf16(const float* queries, int qdim, const float* W, const float* bias, const float* omega,
                              void* out_bf16, int64_t P, int C, float eps_embed, float eps_prenorm, void* stream);
