@@ -53,6 +53,8 @@ SOURCES = {
     "vae.hip": [],
     # fused L1 + SSIM image loss: fmaf only where written, so that equal inputs give equal SSIM numerator and denominator terms
     "loss.hip": ["-ffp-contract=off"],
+    # KNN interpolation loss: the squared distances round operation by operation (neighbour decisions), as in fps.hip
+    "interp.hip": ["-ffp-contract=off"],
 }
 
 

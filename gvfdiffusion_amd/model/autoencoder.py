@@ -148,10 +148,14 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
     # ---- encode (encode_latent.py / training; not on the inference path) ---------------------------------------------
     @staticmethod
     @torch.no_grad()
-    def compute_delta_interp(static_gs, micro_static_pc, micro_moving_pc, knn_k=8, beta=7.0, adaptive_radius=True):
+    def compute_delta_interp(static_gs, micro_static_pc, micro_moving_pc, knn_k=8, beta=7.0, adaptive_radius=True, fused=False):
         """KNN-interpolated motion of the sampled Gaussians (model/autoencoder.py:449-500; pytorch3d.ops.knn_points is a
         brute-force K-nearest search here: squared distances ascending).  static_gs (B,L,3), micro_static_pc (B,N,3),
-        micro_moving_pc (B,T,N,3) -> (B,T,L,3)."""
+        micro_moving_pc (B,T,N,3) -> (B,T,L,3).  fused=True: the HIP search + gather of ops/knn_interp.py (no (B,L,N) distance
+        matrix) instead of the torch composition below; encode() stays on the torch path."""
+        if fused:
+            from ..ops.knn_interp import delta_interp
+            return delta_interp(static_gs, micro_static_pc, micro_moving_pc, k=knn_k, beta=beta, adaptive_radius=adaptive_radius)
         d2 = ((static_gs[:, :, None, :] - micro_static_pc[:, None, :, :]) ** 2).sum(-1)             # (B, L, N)
         knn_dists, knn_idx = torch.topk(d2, knn_k, dim=-1, largest=False, sorted=True)
         radii = knn_dists.mean(dim=-1).sqrt() + 1e-6

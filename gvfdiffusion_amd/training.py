@@ -9,6 +9,9 @@ Here: one process per GPU, each rank renders ITS samples through gvf_rast_forwar
 (gvfdiffusion_amd/rasterizer.py::_RasterizeFn; render_l1_loss) or all views at once through gvf_rast_forward_batched /
 gvf_rast_backward_batched (_RasterizeBatchedFn; render_l1_loss_frames, render_loss_frames), and the gradients of the trainable parameters are averaged with bucketed
 all-reduces on the default process group -- RCCL over xGMI on an MI355X node (backend "nccl"), gloo in the CPU tests.
+The interpolation ("deformation xyz") term of the same step (train_vae.py:304-311, 486-586) is `interpolation_loss`: the KNN search over
+the static anchors, the weighted gather of their motion and the masked L1 against the predicted deltas as fused HIP kernels
+(ops/knn_interp.py: gvf_knn_interp_weights, gvf_interp_loss_forward / _backward), where the reference needs pytorch3d's knn_points.
 The HIP VAE / DiT kernels are inference kernels (no autograd through them); what trains here is whatever torch module
 produces the (T, P, 14) deltas -- `DeltaHead` is the decoder's last projection (model/autoencoder.py `to_outputs`) as a
 plain torch layer over given per-Gaussian features.
@@ -74,6 +77,32 @@ def render_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsics:
     index = list(range(V)) if frame_of_view is None else [int(t) for t in frame_of_view]
     imgs = renderer.render_frames(gaussian, extrinsics, intrinsics, delta_pc=deltas, delta_index=index)["rgb"]
     return image_loss(imgs, targets, l1_weight=l1_weight, ssim_weight=ssim_weight)
+
+
+def interpolation_loss(static_gs: Sequence[torch.Tensor], micro_static_pc: torch.Tensor, micro_moving_pc: torch.Tensor, output: torch.Tensor,
+                       knn_k: int = 8, adaptive_radius: bool = True, beta: float = 7.0):
+    """The reference's interpolation loss (train_vae.py:486-586, compute_interpolation_loss_delta_interp) on the fused HIP operator:
+    static_gs is a list of B ragged (P_b, >= 3) Gaussian tensors (xyz first), micro_static_pc (B, N, 3), micro_moving_pc (B, T, N, 3)
+    absolute positions, output (B, T, >= max P_b, >= 3) the predicted deltas, of which output[b, :, :P_b, :3] is scored against the
+    KNN-interpolated motion of the Gaussians.  Returns (loss, {"deformation_xyz_loss": loss as a detached 1-element tensor},
+    estimated_deltas (B, T, max P_b, 3)); the loss is differentiable in output only, and an output whose third dimension equals
+    max P_b is read in place (no slice copy)."""
+    from .ops.knn_interp import interpolation_l1
+    if len(static_gs) == 0 or len(static_gs) != micro_static_pc.shape[0]:
+        raise ValueError(f"interpolation_loss: {len(static_gs)} Gaussian sets for {micro_static_pc.shape[0]} samples")
+    for g in static_gs:
+        if g.dim() != 2 or g.shape[1] < 3:
+            raise ValueError(f"interpolation_loss: expected (P_b, >= 3) Gaussians, got {tuple(g.shape)}")
+    lengths = [int(g.shape[0]) for g in static_gs]
+    P = max(lengths)
+    if output.dim() != 4 or output.shape[2] < P:
+        raise ValueError(f"interpolation_loss: output {tuple(output.shape)} has fewer than {P} rows per frame")
+    with torch.no_grad():
+        q = torch.stack([F.pad(g[:, :3].float(), (0, 0, 0, P - g.shape[0])) for g in static_gs])
+    pred = output if output.shape[2] == P else output[:, :, :P]
+    loss, est = interpolation_l1(pred, q, micro_static_pc, micro_moving_pc, lengths=lengths, k=knn_k, beta=beta,
+                                 adaptive_radius=adaptive_radius, return_est=True)
+    return loss, {"deformation_xyz_loss": loss.detach().reshape(1)}, est
 
 
 def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20) -> int:
