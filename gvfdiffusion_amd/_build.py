@@ -42,6 +42,8 @@ SOURCES = {
     # tiled-cache cross attention: the issue order of its inner loop is written out (sched_barrier fences), so no scheduler flag
     "attn_xt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
     "attn_xt64.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
+    # attention backward: the same accumulator-as-operand style as the forward (MFMA results feed VALU code and the next MFMA)
+    "attn_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
     "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "gemm256.hip": [],                       # accumulators in AGPRs: 256 of them per wave
     "gemm8.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],

@@ -48,6 +48,12 @@ def scaled_dot_product_attention(*args, **kwargs):
     lp = precision.resolve(tensors=(q, k, v))
     q, k, v = (t if t.dtype == lp else t.to(lp) for t in (q, k, v))
     q, k, v = (t if (t.stride(3) == 1 and t.stride(2) == C) else t.contiguous() for t in (q, k, v))
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        # training: the same forward kernel inside an autograd function whose backward is csrc/attn_bwd.hip; the gradients flow on
+        # through the casts and the unbind views above into the caller's (packed, possibly fp32) tensors
+        from ...ops import attention_grad
+        out = attention_grad.attention(q, k, v)
+        return out if dt == lp else out.to(dt)
     out = torch.empty((N, Lq, H, C), dtype=lp, device=q.device)
     dit_ops.attention(q, k, v, out, N, 1, Lq, k.shape[1], H, _strides(q), _strides(k), _strides(v), _strides(out), head_dim=C)
     return out if dt == lp else out.to(dt)

@@ -12,9 +12,12 @@ all-reduces on the default process group -- RCCL over xGMI on an MI355X node (ba
 The interpolation ("deformation xyz") term of the same step (train_vae.py:304-311, 486-586) is `interpolation_loss`: the KNN search over
 the static anchors, the weighted gather of their motion and the masked L1 against the predicted deltas as fused HIP kernels
 (ops/knn_interp.py: gvf_knn_interp_weights, gvf_interp_loss_forward / _backward), where the reference needs pytorch3d's knn_points.
-The HIP VAE / DiT kernels are inference kernels (no autograd through them); what trains here is whatever torch module
-produces the (T, P, 14) deltas -- `DeltaHead` is the decoder's last projection (model/autoencoder.py `to_outputs`) as a
-plain torch layer over given per-Gaussian features.
+Attention trains through its HIP kernels: with grad enabled, model/attention/full_attn.py::scaled_dot_product_attention runs the
+inference forward inside an autograd function whose backward is csrc/attn_bwd.hip (ops/attention_grad.py), so a reference-style
+transformer block -- torch nn.Linear / LayerNorm / MultiHeadRMSNorm around that operator -- trains on this package; the projections
+and norms around it are torch's, and the fused GEMM / row-block kernels of the inference path carry no gradient.  `DeltaHead` is the
+smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
+per-Gaussian features, producing the (T, P, 14) deltas.
 """
 from typing import Callable, Iterable, List, Optional, Sequence
 

@@ -1,0 +1,51 @@
+/*
+ * gvf_attn_bwd.h -- C ABI of the attention backward (csrc/attn_bwd.hip): dQ, dK, dV of
+ *     out = softmax(q k^T * scale) v,     head_dim 32 or 64, no mask, no dropout, scale > 0,
+ * the gradient of gvf_attn_fwd (gvf_dit.h) without its fused RMSNorm gains and with row-major v.
+ *
+ * Tensors are 16-bit (`dtype`: GVF_DT_BF16 / GVF_DT_F16 of gvf_dit.h) and addressed as in gvf_attn_fwd: batch index = (outer, inner),
+ * 4 strides in elements {outer, inner, seq, head}, element (o,i,l,h,c) at o*s[0] + i*s[1] + l*s[2] + h*s[3] + c, so the q / k / v
+ * slices of a packed qkv or kv projection are read in place.  q, out, dout, dq have Lq rows, k, v, dk, dv have Lk rows; any
+ * lengths >= 1.  Input bases and strides keep 16-byte alignment (8 elements), gradient bases and strides 8 bytes (4 elements).
+ *
+ * Method: P is recomputed from q, k and a per-row log-sum-exp.  A statistics pass writes lse2 = log2 sum_k exp2(c s_k), c = scale log2 e,
+ * and delta = sum_d dout_d out_d (fp32, (N, H, Lq) each) into the workspace; one sweep has a workgroup own a key block and walk the
+ * queries (dk, dv), one has it own a query block and walk the keys (dq).  Sequences with Lq, Lk <= 32 and head_dim 32 take one wave
+ * per (sequence, head) and touch no workspace.
+ * Rounding: scores and dP = dout v^T fp32 from the 16-bit operands; p = exp2(c s - lse2) fp32, rounded to 16 bit where it feeds dv;
+ * dS = p (dP - delta) scale rounded to 16 bit where it feeds dq and dk; fp32 accumulation; gradients stored in the operand type.
+ * With few key blocks and many queries the key sweep splits the query range over several workgroups per key block, by a rule of the
+ * shape alone; their fp32 partial dk / dv (in the workspace) are added in chunk order by one more kernel and rounded once.
+ * Determinism: every gradient element is summed in a fixed order -- no float atomics, no waiting between workgroups -- so two calls
+ * on the same inputs give bit-identical gradients.
+ *
+ * Conventions as in gvf_loss.h: device pointers, an explicit stream (null = the default stream), no host synchronisation and no
+ * allocation, an int status.  Every argument is checked on the host before any launch; GVF_EINVAL for a null pointer, a head_dim
+ * other than 32 / 64, a dtype that is not a 16-bit type, a non-positive count or length, a misaligned base or stride, scale <= 0,
+ * or a workspace smaller than gvf_attn_bwd_workspace_bytes reports.
+ */
+#ifndef GVF_ATTN_BWD_H
+#define GVF_ATTN_BWD_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Bytes of the caller-owned workspace of one gvf_attn_bwd call (the row statistics and, for a split key sweep, the partial
+ * sums): host only.  The workspace must be 16-byte aligned. */
+int gvf_attn_bwd_workspace_bytes(int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim, size_t* out);
+
+int gvf_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout,
+                 void* dq, void* dk, void* dv,
+                 int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim,
+                 const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                 const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides,
+                 float scale, void* workspace, size_t workspace_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GVF_ATTN_BWD_H */
