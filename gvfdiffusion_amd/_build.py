@@ -22,13 +22,14 @@ LIB_PATH = os.path.join(_HERE, "libgvf_hip.so")
 # packed instructions without any vectoriser.)
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize",
           "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-# per-source extra flags.  rast.hip: the floating-point contract shared with oracle/rast_oracle.c
+# per-source extra flags.  rast*.hip: the floating-point contract shared with oracle/rast_oracle.c
 # (no implicit fma contraction; fmaf only where written).
 SOURCES = {
     "sort.hip": [],
-    # -fno-slp-vectorize: left on, clang packs neighbouring scalar fp32 operations of the compositing loop into
-    # v_pk_* instructions (4 cycles each against 2.8 for the scalar form, plus the v_mov traffic that builds the pairs)
     "rast.hip": ["-ffp-contract=off"],
+    "rast_sort.hip": ["-ffp-contract=off"],
+    "rast_blend.hip": ["-ffp-contract=off"],
+    "rast_bwd.hip": ["-ffp-contract=off"],
     "vox2seq.hip": [],
     "resize.hip": [],
     # the squared distances must round exactly as the oracle's binary32 expression does (index-exact parity)
@@ -37,7 +38,7 @@ SOURCES = {
     # read/write traffic between the MFMAs and the softmax / epilogue VALU code.
     # -fno-honor-nans: no canonicalising v_max in front of fmaxf (infinities stay honoured: -inf masks keys).
     # iterative-ilp: the scheduler variant that measured best for the attention kernels in the denoise step (8.5 -> 8.4 ms
-    # per NFE; max-ilp and the default are slower; for rast.hip every non-default strategy slows the blend)
+    # per NFE; max-ilp and the default are slower; for rast_blend.hip every non-default strategy slows the blend)
     "attn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
     # tiled-cache cross attention: the issue order of its inner loop is written out (sched_barrier fences), so no scheduler flag
     "attn_xt.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form", "-fno-honor-nans"],
@@ -87,9 +88,11 @@ def raster_source_hash() -> str:
     """sha256 over the sources of the rasteriser kernels only: stamps profiles/*_pmc_raster.json so that bench.py can tell
     whether the committed HBM-traffic counters were taken on the kernels it is running."""
     import hashlib
+    import glob
     inc = os.path.join(os.path.dirname(_HERE), "include")
     h = hashlib.sha256()
-    for f in (os.path.join(CSRC, "rast.hip"), os.path.join(CSRC, "sort.hip"), os.path.join(CSRC, "gvf_common.h"), os.path.join(inc, "gvf_rast.h")):
+    for f in sorted(glob.glob(os.path.join(CSRC, "rast*.hip")) + glob.glob(os.path.join(CSRC, "rast*.h"))) + \
+            [os.path.join(CSRC, "sort.hip"), os.path.join(CSRC, "gvf_common.h"), os.path.join(inc, "gvf_rast.h")]:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()
@@ -157,7 +160,7 @@ def build_variant(name: str, defines: dict, verbose: bool = False) -> str:
 if __name__ == "__main__":
     import sys
     if len(sys.argv) >= 3 and sys.argv[1] == "--variant":
-        # python -m gvfdiffusion_amd._build --variant ring4 attn_xt.hip=-DXT_RING_STAGES=4 [rast.hip=-DFOO=1,-DBAR=2 ...]
+        # python -m gvfdiffusion_amd._build --variant ring4 attn_xt.hip=-DXT_RING_STAGES=4 [rast_blend.hip=-DFOO=1,-DBAR=2 ...]
         print(build_variant(sys.argv[2], {a.split("=", 1)[0]: a.split("=", 1)[1].split(",") for a in sys.argv[3:]}, verbose=True))
     else:
         print(build(force=False, verbose=True))

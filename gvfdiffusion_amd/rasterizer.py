@@ -2,7 +2,7 @@
 
 Reference seam: renderers/gaussian_render.py:110-143 (settings) and :198-220 (operator call) --
 the reference imports the two classes from the external CUDA packages `diff_gaussian_rasterization`
-(mip-splatting fork) and `diff_gauss`; here they are backed by libgvf_hip.so (csrc/rast.hip).
+(mip-splatting fork) and `diff_gauss`; here they are backed by libgvf_hip.so (csrc/rast*.hip).
 Differentiable: when an input requires grad, rasterize() runs through _RasterizeFn (forward keeps its
 workspace, backward calls gvf_rast_backward) -- upstream's _RasterizeGaussians autograd.Function -- and
 rasterize_batched() through _RasterizeBatchedFn (gvf_rast_backward_batched: gradients of the raw GaussianModel

@@ -1,7 +1,7 @@
 """Real spherical-harmonics basis, degrees 0-3, with the reference's conventions
 (renderers/sh_utils.py:26-112: same coefficient ordering and signs; RGB2SH/SH2RGB :114-117).
 Host-side helper for the `convert_SHs_python` branch and for building synthetic inputs; the
-rasteriser evaluates SH in its preprocess kernel (csrc/rast.hip sh_to_rgb)."""
+rasteriser evaluates SH in its preprocess kernel (csrc/rast_common.h sh_to_rgb)."""
 import torch
 
 C0 = 0.28209479177387814

@@ -489,7 +489,7 @@ int gvfo_render_brute(int P, int M, int deg, const float* means3D, const float* 
     return 0;
 }
 
-/* ---- exp / log1p of the activations: ONE arithmetic, written here and in gvfdiffusion_amd/csrc/rast.hip (act_expf / act_log1pf) --------
+/* ---- exp / log1p of the activations: ONE arithmetic, written here and in gvfdiffusion_amd/csrc/rast_common.h (act_expf / act_log1pf) --------
  * gaussian_model.py:84-114 activates with torch's exp / softplus (= log1p(exp(x)) below its threshold of 20) / sigmoid.  Up to round 5 the
  * oracle called libm (expf, log1pf) and the device its own math library: the two agree to an ulp or two, and at 262 144 Gaussians x 24 frames
  * a few radii and tile rects flipped, so the full-size delta-frame tests could not hold the exact-radii rule.  Now both

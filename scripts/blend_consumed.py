@@ -1,5 +1,5 @@
 """How much of the per-tile sort's output does the blend look at?    Needs the BLEND_CONSUMED variant library:
-    python -m gvfdiffusion_amd._build --variant blendc rast.hip=-DBLEND_CONSUMED
+    python -m gvfdiffusion_amd._build --variant blendc rast_blend.hip=-DBLEND_CONSUMED
     GVF_LIB=gvfdiffusion_amd/variants/libgvf_hip_blendc.so python scripts/blend_consumed.py [live|bench]
 Per size class of a (frame, tile) segment: segments, keys sorted, keys staged by the compositing loop when every pixel of the tile was saturated
 (whole 256-key rounds), and the ratio -- for the reference's live render shape (one 96-frame chunk: 512^2, SH 0, 262 144 Gaussians) or the bench shape."""

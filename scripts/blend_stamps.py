@@ -1,5 +1,5 @@
 """Wave-cycles per phase of blend_kernel on the bench shape (BASELINE configs[1]) -- needs the BLEND_TIMING variant library:
-    python -m gvfdiffusion_amd._build --variant blendt rast.hip=-DBLEND_TIMING
+    python -m gvfdiffusion_amd._build --variant blendt rast_blend.hip=-DBLEND_TIMING
     GVF_LIB=gvfdiffusion_amd/variants/libgvf_hip_blendt.so python scripts/blend_stamps.py
 Forcing s_waitcnt vmcnt(0) between the phases perturbs the schedule (the product overlaps the id load, the gather and the staging
 arithmetic of one wave only through other waves anyway); the figures are shares of the waves' resident time, not product timings."""

@@ -6,7 +6,9 @@
 # e.g.  scripts/gpu_ab.sh gpurun_out/r05/prefetch_ab.txt 3 dit "GVF_DIT_PREFETCH=1" "GVF_DIT_PREFETCH=0"
 # A variant may rebuild the library first:  "REBUILD='-DXT_RING_STAGES=4' ..."  is NOT supported here on purpose -- build the variants as
 # separate .so files before the call and select them with GVF_LIB=<path> (gvfdiffusion_amd/_lib.py).
-set -u
+# Every run has its own time limit and its exit status is checked: the first failure ends the script (no further program is started on a
+# card that may have faulted), as in scripts/evidence.sh.
+set -u -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 OUT=${1:?out}; REPS=${2:?reps}; LEG=${3:?leg}; shift 3
 mkdir -p "$(dirname "$OUT")"
@@ -21,7 +23,9 @@ esac
 for rep in $(seq 1 $REPS); do
   for V in "$@"; do
     echo -n "[$V] " >> "$OUT"
-    env $V timeout 900 python bench.py $ARGS 2>>"$OUT.err" | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); $PY" >> "$OUT" 2>&1
+    env $V timeout -k 10 900 python bench.py $ARGS 2>>"$OUT.err" | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); $PY" >> "$OUT" 2>&1
+    rc=$?
+    if [ $rc -ne 0 ]; then cat "$OUT"; echo "gpu_ab.sh: [$V] failed (exit status $rc); stopping" >&2; exit $rc; fi
   done
 done
 cat "$OUT"

@@ -1,5 +1,5 @@
 """How many per-tile segments does the distribution sort hand to the sorting network (a bucket of more than BKT_MAX_RUN keys)?  Needs the SORT_STATS variant:
-    python -m gvfdiffusion_amd._build --variant sortstats rast.hip=-DSORT_STATS
+    python -m gvfdiffusion_amd._build --variant sortstats rast_sort.hip=-DSORT_STATS
     GVF_LIB=gvfdiffusion_amd/variants/libgvf_hip_sortstats.so python scripts/sort_stats.py [live|bench]"""
 import ctypes, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

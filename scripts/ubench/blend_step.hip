@@ -1,4 +1,4 @@
-// blend_step.hip -- VERDICT r5 item 9: a LOOP-ONLY benchmark of blend_kernel's compositing step (csrc/rast.hip GVF_BLEND_STEP), 4 waves per
+// blend_step.hip -- VERDICT r5 item 9: a LOOP-ONLY benchmark of blend_kernel's compositing step (csrc/rast_blend.hip GVF_BLEND_STEP), 4 waves per
 // workgroup = four 8 x 8 quadrants, 8 workgroups per CU (the launch's residency), over a synthetic per-wave list of 256 entries in LDS:
 //   MODE 0  today's step: 3 ds_read_b128 + 16 vector instructions per list entry (exponent from the Cholesky factor, v_exp_f32, two predicates,
 //           3 colour fmas, T update), 4 entries per trip
@@ -6,7 +6,7 @@
 //           (x^2, xy, y^2, x, y, 1) -- lane = pixel, the accumulator's four registers = the pixel's four splats --, computed one group AHEAD of
 //           the compositing, which is then 11 vector instructions per entry
 //   MODE 2  today's arithmetic with the step's predicates kept as explicit 64-bit lane masks (ballot / inverse ballot): 6 scalar instructions fewer per
-//           trip of four entries -- what csrc/rast.hip's blend_kernel runs (lane masks)
+//           trip of four entries -- what csrc/rast_blend.hip's blend_kernel runs (lane masks)
 //   MODE 3  MODE 2 + the 0.99 clamp on v_exp_f32's output modifier (15 vector instructions; not bit-identical): no further gain
 //   MODE 4/5  MODE 2 with the trip's LDS reads first and ONE s_waitcnt (/ the next trip's list words ahead): slower -- a s_waitcnt is not an issue slot
 //   MODE 6  MODE 2 with the trip's two exits kept apart by a non-speculatable asm statement: the structuriser rebuilds the same 9-10 scalar instructions

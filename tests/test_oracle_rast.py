@@ -184,7 +184,7 @@ def test_golden_activations(oracle_lib):
 
 def test_shared_activation_arithmetic_stays_within_2ulp_of_libm(oracle_lib):
     """oracle/rast_oracle.c::act_expf / act_log1pf -- the exp and log1p the activations are computed with since round 6, the SAME operation
-    sequence as csrc/rast.hip's (the device is held to it bit for bit in tests/test_rast_gpu.py::test_activation_kernel_matches_oracle) -- against
+    sequence as csrc/rast_common.h's (the device is held to it bit for bit in tests/test_rast_gpu.py::test_activation_kernel_matches_oracle) -- against
     float64 (each function < 1 ulp of the true value) and against this box's libm (expf, log1pf through ctypes: <= 2 ulps apart, the two being
     within an ulp of the truth each); softplus = log1p(exp(x)) as gaussian_model.py:84-114 composes it: <= 2 ulp of the true value.  Special
     values: NaN propagates, +-inf, the overflow / underflow ends, 0."""

@@ -187,7 +187,7 @@ def test_activation_kernel_matches_oracle(cuda, oracle_lib):
                                                None if delta is None else delta.numpy(), aabb=[-0.5, -0.5, -0.5, 1, 1, 1],
                                                scale_bias=act.scale_bias, opacity_bias=act.opacity_bias,
                                                min_kernel_size=0.0009, scaling_activation=act.scaling_activation)
-            # everything is bit-exact -- exp / log1p included since round 6: csrc/rast.hip and oracle/rast_oracle.c evaluate ONE operation
+            # everything is bit-exact -- exp / log1p included since round 6: csrc/rast_common.h and oracle/rast_oracle.c evaluate ONE operation
             # sequence (act_expf / act_log1pf; up to round 5 two different libms, relative 2e-6)
             for k in ("means3D", "rotations", "shs", "scales"):
                 assert np.array_equal(out[k].cpu().numpy(), ref[k]), k

@@ -1,6 +1,6 @@
 """The per-tile half of the rasteriser's sort stage on its own: every segment must come out in
 upstream's stable (tile, depth) order = ascending (depth bits, Gaussian id), for every size class and for depth
-distributions that defeat the distribution sort (csrc/rast.hip tile_sort_buckets) and send the segment through the network."""
+distributions that defeat the distribution sort (csrc/rast_sort.hip tile_sort_buckets) and send the segment through the network."""
 import numpy as np
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""The exactness argument of the per-tile distribution sort (csrc/rast.hip tile_sort_buckets), checked on the CPU in the kernel's own
+"""The exactness argument of the per-tile distribution sort (csrc/rast_sort.hip tile_sort_buckets), checked on the CPU in the kernel's own
 float32 arithmetic: the bucket of a key is a monotone function of the key's high word (the depth bits taken as an unsigned integer), so
 keys of a lower bucket sort before keys of a higher one whatever the bit patterns are, and bucket order + exact ranks inside a bucket
 give the sorted order."""
