@@ -58,6 +58,8 @@ SOURCES = {
     "loss.hip": ["-ffp-contract=off"],
     # KNN interpolation loss: the squared distances round operation by operation (neighbour decisions), as in fps.hip
     "interp.hip": ["-ffp-contract=off"],
+    # fused clip + AdamW + EMA step: one rounding per written operation (the conformance bars count them)
+    "optim.hip": ["-ffp-contract=off"],
 }
 
 

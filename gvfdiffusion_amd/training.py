@@ -19,6 +19,7 @@ and norms around it are torch's, and the fused GEMM / row-block kernels of the i
 smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
 per-Gaussian features, producing the (T, P, 14) deltas.
 """
+import sys
 from typing import Callable, Iterable, List, Optional, Sequence
 
 import torch
@@ -108,16 +109,27 @@ def interpolation_loss(static_gs: Sequence[torch.Tensor], micro_static_pc: torch
     return loss, {"deformation_xyz_loss": loss.detach().reshape(1)}, est
 
 
-def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20) -> int:
+def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20, flat=None) -> int:
     """DDP's gradient averaging, explicit: grads are packed into flat buckets of <= bucket_bytes (few, large collectives:
     a ring all-reduce over xGMI is per-link bound, so small messages waste it), summed over the ranks with
     all_reduce and divided by the world size; parameters without a gradient contribute zeros, so every rank issues the
-    same collectives.  Returns the number of collectives.  No-op when torch.distributed is not initialised."""
+    same collectives.  Returns the number of collectives.  No-op when torch.distributed is not initialised.
+    flat: an ops.optim.FlatGrads that owns(params) -- the gradients already ARE one flat buffer, which is all-reduced in place in
+    slices of <= bucket_bytes (no cat, no copy back) and divided by the world size; returns the number of slices."""
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()):
         return 0
     world = dist.get_world_size(group)
     plist: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
+    if flat is not None and flat.owns(plist):
+        n_coll = 0
+        for buf in flat.buffers.values():
+            per = max(1, bucket_bytes // buf.element_size())
+            for a in range(0, buf.numel(), per):
+                dist.all_reduce(buf[a:a + per], op=dist.ReduceOp.SUM, group=group)
+                n_coll += 1
+            buf.div_(world)
+        return n_coll
     n_coll, i = 0, 0
     while i < len(plist):
         bucket, nbytes = [], 0
@@ -142,7 +154,20 @@ def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket
 def train_step(params: Sequence[torch.nn.Parameter], optimizer: torch.optim.Optimizer, loss_fn: Callable[[], torch.Tensor],
                max_grad_norm: float = 1.0, group=None) -> dict:
     """zero_grad -> loss = loss_fn() on this rank's samples -> backward -> gradient all-reduce (mean over ranks) ->
-    clip_grad_norm_(max_grad_norm) -> optimizer.step   (train_latent.py:183-215)."""
+    clip_grad_norm_(max_grad_norm) -> optimizer.step   (train_latent.py:183-215).
+    With an ops.optim.FusedAdamW the norm, the clip, the AdamW update and the EMAs are the optimizer's one fused device-side step
+    (optimizer.max_grad_norm is set from the argument), the all-reduce runs in place on its flat gradient buffer, and the returned
+    dict has a further key "found_inf" (1: a non-finite gradient norm, the step was skipped on the device)."""
+    fused = sys.modules.get(__package__ + ".ops.optim")    # never imported: the optimizer cannot be one of its class, and the old path imports nothing
+    if fused is not None and isinstance(optimizer, fused.FusedAdamW):
+        optimizer.zero_grad()
+        loss = loss_fn()
+        loss.backward()
+        n = allreduce_gradients(params, group=group, flat=optimizer.flat_grads)
+        optimizer.max_grad_norm = max_grad_norm
+        optimizer.step()
+        return {"loss": float(loss.detach()), "grad_norm": float(optimizer.grad_norm), "collectives": n,
+                "found_inf": int(optimizer.found_inf)}
     optimizer.zero_grad(set_to_none=True)
     loss = loss_fn()
     loss.backward()
