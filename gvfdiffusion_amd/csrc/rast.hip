@@ -13,6 +13,7 @@
 //   bbox, morton_count/scan/scatter      once per call: 15-bit Morton order of the Gaussians (locality for the bin passes)
 //   preprocess   grid (ceil(P/256), F/4) activations (+deltas), EWA covariance, 2D filter, radius, tile rect, alpha-box
 //                                        instance culling, SH -> RGB; writes one 64-byte splat record + a 16-byte bin record
+//                                        (without shared activation: grid (ceil(P/64), ceil(F/24)), one frame per wave at a time)
 //   bin<count>   grid (ceil(P/1024), F)  per-(frame, tile) instance counts: LDS histogram per block, one global atomic
 //                                        per touched tile
 //   seg_sums, seg_scan, frame_counts     exclusive scan of the counters = tile ranges + cursors, per-frame D, overflow guard
@@ -48,6 +49,15 @@ namespace {
 #endif
 constexpr int PRE_FB = GVF_PRE_FB;   // frames per preprocess workgroup: the frame-invariant inputs (xyz, scale, rotation, opacity,
                             // SH: 164 of the 220 input bytes per Gaussian at degree 2) come from HBM once per PRE_FB frames
+// Wave-frames mapping (preprocess_kernel<false, true>, the bucket-binning launch without shared activation): 64 Gaussians per workgroup, each of
+// its PRE_WAVES waves walks PRE_WAVE_FB frames, so the frame-invariant inputs come from HBM once per PRE_WAVES * PRE_WAVE_FB = 24 frames on
+// a grid that keeps ceil(P / 64) workgroups per frame group.  Against PRE_FB = 4 on the 256-Gaussian mapping the launch takes 240 us instead
+// of 275 at 24 frames; 3 frames per wave (twice as many, shorter workgroups) is not faster (profiles/r14_preprocess_wave_frames_ab.txt).
+#ifndef GVF_PRE_WAVE_FB
+#define GVF_PRE_WAVE_FB 6
+#endif
+constexpr int PRE_WAVES = PRE_THREADS / GVF_WAVE;
+constexpr int PRE_WAVE_FB = GVF_PRE_WAVE_FB;
 // preprocess_kernel runs on a (Gaussian blocks, frame groups) grid.  Measured and not adopted (profiles/r05_preprocess_variants_ab.txt): an
 // XCD-aware workgroup order and requesting the next frame's delta row ahead -- the launch waits neither on L2 hits nor on bytes in flight.
 // The fused launch reads its delta rows straight from global memory: staging them through LDS costs occupancy and is slower
@@ -181,7 +191,12 @@ __device__ __forceinline__ TileRect tight_rect(TileRect r, float px, float py, f
 }
 
 // SHARED: a0 = the stage-A records [slices][P][4 x float4] (see activate_cov_kernel), frames[f].reserved[0] = the frame's slice
-template <bool SHARED>
+// WAVE_FRAMES (bucket binning without shared activation; block_sums and tiles_touched are null by construction): the workgroup owns 64
+// consecutive Gaussians instead of 256 and its four waves walk different frames -- wave w takes frames 4 G by + w + 4 ff, ff = 0 .. G - 1
+// (G = PRE_WAVE_FB) -- so the SH rows are staged once per 4 G frames and the raw inputs come across the fabric once per 4 G frames, on a grid
+// that keeps ceil(P / 64) x ceil(F / 4G) workgroups.  One barrier, after the staging; the waves never meet again.  What a wave loads and stores
+// per frame (delta rows, quad-transposed splat records, bin records) and the per-Gaussian arithmetic are those of the other mapping.
+template <bool SHARED, bool WAVE_FRAMES = false>
 __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     PreParams pp, const GvfRastFrame* __restrict__ frames, const float* __restrict__ a0,
     const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ a3,
@@ -190,19 +205,22 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     uint32_t* __restrict__ tiles_touched,
     int32_t* __restrict__ radii, uint32_t* __restrict__ block_sums, uint4* __restrict__ binrec,
     const uint32_t* __restrict__ bin_slot /* Gaussian -> position of its bin record inside a frame; null = identity */) {
-    extern __shared__ __attribute__((aligned(16))) float sh_lds[];  // [PRE_THREADS][M*3] + 4 wave sums
+    static_assert(!(SHARED && WAVE_FRAMES), "the shared-activation launch keeps the 256-Gaussian mapping");
+    extern __shared__ __attribute__((aligned(16))) float sh_lds[];  // [PRE_GPB][M*3] + 4 wave sums
+    constexpr int PRE_GPB = WAVE_FRAMES ? GVF_WAVE : PRE_THREADS;   // Gaussians per workgroup
     const int t = threadIdx.x;
     const int P = pp.P, M = pp.M;
     const int nbx = (P + PRE_THREADS - 1) / PRE_THREADS;
     const int bx = blockIdx.x, by = blockIdx.y;
-    const int i = bx * PRE_THREADS + t;
+    const int row = WAVE_FRAMES ? (t & (GVF_WAVE - 1)) : t;        // this thread's Gaussian inside the workgroup (= its SH row in LDS)
+    const int i = bx * PRE_GPB + row;
 
-    // Stage this block's SH coefficients through LDS with coalesced 16-byte loads: 256 Gaussians x
+    // Stage this block's SH coefficients through LDS with coalesced 16-byte loads: PRE_GPB Gaussians x
     // M*3 floats are one contiguous span of the [P][M][3] tensor.
     const int sh_stride = M * 3;
     if (sh != nullptr) {
-        const size_t span0 = (size_t)bx * PRE_THREADS * sh_stride;
-        const int nvalid = min(PRE_THREADS, P - bx * PRE_THREADS);
+        const size_t span0 = (size_t)bx * PRE_GPB * sh_stride;
+        const int nvalid = min(PRE_GPB, P - bx * PRE_GPB);
         const int total = nvalid * sh_stride;
         const float4* src4 = reinterpret_cast<const float4*>(sh + span0);  // span0*4 B is 16-B aligned
         float4* dst4 = reinterpret_cast<float4*>(sh_lds);
@@ -213,8 +231,17 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     __syncthreads();
 
   const uint32_t my_slot = (bin_slot != nullptr && i < P) ? bin_slot[i] : (uint32_t)i;
-  for (int ff = 0; ff < PRE_FB; ++ff) {
-    const int f = by * PRE_FB + ff;
+  // wave-frames mapping: the raw parameters and their delta-independent first operations once, in front of the frame loop (78 -> 90 vector
+  // registers, 5 waves per SIMD as on the other mapping: -23 us per launch at 24 frames)
+  ActRaw raw = {};
+  if (WAVE_FRAMES && pp.fused && i < P) raw = activate_raw(i, pp.act, a0, a1, a2, a3);
+  // first frame, frame stride and frame count of this thread's wave.  The wave index goes through readfirstlane: the frame index must be
+  // a scalar, or the camera block (frames[f]: 40 floats) is fetched with per-lane loads into vector registers instead of s_load into scalars
+  const int f_first = WAVE_FRAMES ? by * (PRE_WAVES * PRE_WAVE_FB) + __builtin_amdgcn_readfirstlane(t >> 6) : by * PRE_FB;
+  constexpr int F_STEP = WAVE_FRAMES ? PRE_WAVES : 1, F_COUNT = WAVE_FRAMES ? PRE_WAVE_FB : PRE_FB;
+#pragma unroll 1
+  for (int ff = 0; ff < F_COUNT; ++ff) {
+    const int f = f_first + ff * F_STEP;
     if (f >= pp.F) break;
     const GvfRastFrame* fr = frames + f;
     uint32_t touched = 0;
@@ -234,7 +261,15 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
         } else if (pp.fused) {
             const int di = fr->delta_index;
             const float* d = (delta != nullptr && di >= 0) ? delta + ((size_t)di * P + i) * 14 : nullptr;
-            ActGaussian g = activate_one(i, pp.act, a0, a1, a2, a3, d);
+            ActGaussian g;
+            if (WAVE_FRAMES) {
+                float dl[14];
+#pragma unroll
+                for (int k = 0; k < 14; ++k) dl[k] = d ? d[k] : 0.0f;
+                g = activate_finish(raw, pp.act, dl, d != nullptr);
+            } else {
+                g = activate_one(i, pp.act, a0, a1, a2, a3, d);
+            }
 #pragma unroll
             for (int k = 0; k < 3; ++k) { p[k] = g.p[k]; s[k] = g.s[k]; dadd[k] = g.drgb[k]; }
 #pragma unroll
@@ -331,7 +366,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
                         rgb[1] = colors_precomp[3 * (size_t)i + 1];
                         rgb[2] = colors_precomp[3 * (size_t)i + 2];
                     } else {
-                        sh_to_rgb(pp.deg, sh_lds + t * sh_stride, dadd, p, fr->campos, rgb);
+                        sh_to_rgb(pp.deg, sh_lds + row * sh_stride, dadd, p, fr->campos, rgb);
                     }
                     radius_out = (int)my_radius;
                     const float2 ext = cull_extent(ca, cb, cc, op * coef);
@@ -348,7 +383,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
             }
         }
         const size_t o = (size_t)f * P + i;
-        if (tiles_touched != nullptr) tiles_touched[o] = touched;   // radix binning only
+        if (!WAVE_FRAMES && tiles_touched != nullptr) tiles_touched[o] = touched;   // radix binning only
         if (radii != nullptr) {
             // slot order (SHARED with a1 = the slot -> Gaussian table): thread i works on slot i, the radii stay indexed by Gaussian
             const uint32_t* gid_of = SHARED ? reinterpret_cast<const uint32_t*>(a1) : nullptr;
@@ -384,7 +419,7 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
 #undef GVF_QB
 
     // block sum of tiles_touched (feeds the instance-offset scan, R2; radix binning only)
-    if (block_sums != nullptr) {
+    if (!WAVE_FRAMES && block_sums != nullptr) {
         const unsigned lane = t & 63, w = t >> 6;
         uint32_t incl = gvf_wave_incl_scan(touched, lane);
         __shared__ uint32_t wsum[PRE_THREADS / GVF_WAVE];
@@ -921,6 +956,9 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
     std::vector<int> frame_slice((size_t)F, 0);
     const char* shared_env = getenv("GVF_RAST_SHARED_ACT");          // read per call: tests switch it inside one process
     const bool shared_on = !(shared_env && shared_env[0] == '0');
+    // GVF_RAST_PRE_WAVE_FRAMES=0: test switch, the bucket-binning fused launch on the 256-Gaussian mapping (preprocess_kernel<false>)
+    const char* wf_env = getenv("GVF_RAST_PRE_WAVE_FRAMES");         // read per call, like the switch above
+    const bool wave_frames_on = !(wf_env && wf_env[0] == '0');
     if (shared_on && fused && cov3D_precomp == nullptr && st.bin_algo != GVF_RAST_BIN_RADIX && P > 0 && F >= 2) {
         shared = true;
         for (int f = 0; f < F && shared; ++f) {
@@ -1019,6 +1057,13 @@ int run_pipeline(const GvfRastSettings& st, const GvfRastFrame* frames_host, int
                                w.frames, reinterpret_cast<const float*>(rec3d), nullptr, nullptr, nullptr, colors_precomp ? nullptr : sh, colors_precomp,
                                nullptr, nullptr, w.splats, nullptr, out_radii == nullptr ? nullptr : w.radii, nullptr, w.binrec,
                                order != nullptr ? w.order_alt : nullptr);
+        } else if (bucket && wave_frames_on) {
+            // wave-frames mapping (preprocess_kernel<false, true>): 64 Gaussians and their SH rows per workgroup, one frame per wave at a time
+            const size_t wf_lds_bytes = gvf_align_up((size_t)GVF_WAVE * pp.M * 3 * sizeof(float), 16) + 16;
+            const dim3 wf_grid((P + GVF_WAVE - 1) / GVF_WAVE, (F + PRE_WAVES * PRE_WAVE_FB - 1) / (PRE_WAVES * PRE_WAVE_FB));
+            hipLaunchKernelGGL((preprocess_kernel<false, true>), wf_grid, dim3(PRE_THREADS), wf_lds_bytes, stream, pp,
+                               w.frames, a0, a1, a2, a3, colors_precomp ? nullptr : sh, colors_precomp, cov3D_precomp, delta,
+                               w.splats, nullptr, out_radii == nullptr ? nullptr : w.radii, nullptr, w.binrec, nullptr);
         } else
         hipLaunchKernelGGL(preprocess_kernel<false>, pre_grid, dim3(PRE_THREADS), sh_lds_bytes, stream, pp,
                            w.frames, a0, a1, a2, a3, colors_precomp ? nullptr : sh, colors_precomp, cov3D_precomp, delta,

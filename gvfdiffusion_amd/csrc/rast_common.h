@@ -123,40 +123,60 @@ struct ActGaussian {
     float p[3], s[3], q[4], op, drgb[3];
 };
 
+// The raw parameters of one Gaussian after the operations that do not depend on the delta row: a launch that walks several frames per thread
+// (preprocess_kernel<false, true>) loads them once and finishes the activation per frame.
+struct ActRaw {
+    float p[3], s[3], q[4], op;
+};
+__device__ __forceinline__ ActRaw activate_raw(int i, const GvfGaussianActivation& a,
+                                               const float* __restrict__ xyz_raw,
+                                               const float* __restrict__ scaling_raw,
+                                               const float* __restrict__ rotation_raw,
+                                               const float* __restrict__ opacity_raw) {
+    ActRaw r;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.p[k] = xyz_raw[3 * (size_t)i + k] * a.aabb[3 + k] + a.aabb[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r.s[k] = scaling_raw[3 * (size_t)i + k] + a.scale_bias;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r.q[k] = rotation_raw[4 * (size_t)i + k] + (k == 0 ? 1.0f : 0.0f);
+    r.op = opacity_raw[i] + a.opacity_bias;
+    return r;
+}
 // dl: the delta row (zeros when d is false -- they are not added then, as the reference's get_* accessors do without a delta)
-__device__ __forceinline__ ActGaussian activate_vals(int i, const GvfGaussianActivation& a,
-                                                     const float* __restrict__ xyz_raw,
-                                                     const float* __restrict__ scaling_raw,
-                                                     const float* __restrict__ rotation_raw,
-                                                     const float* __restrict__ opacity_raw,
-                                                     const float (&dl)[14], bool d) {
+__device__ __forceinline__ ActGaussian activate_finish(const ActRaw& r, const GvfGaussianActivation& a, const float (&dl)[14], bool d) {
     ActGaussian g;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float v = xyz_raw[3 * (size_t)i + k] * a.aabb[3 + k] + a.aabb[k];
-        g.p[k] = d ? v + dl[k] : v;
-    }
+    for (int k = 0; k < 3; ++k) g.p[k] = d ? r.p[k] + dl[k] : r.p[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        float x = scaling_raw[3 * (size_t)i + k] + a.scale_bias;
+        float x = r.s[k];
         if (d) x = x + dl[3 + k];
         g.s[k] = act_scale(x, a);
     }
     float q[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        q[k] = rotation_raw[4 * (size_t)i + k] + (k == 0 ? 1.0f : 0.0f);
+        q[k] = r.q[k];
         if (d) q[k] = q[k] + dl[6 + k];
     }
     float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     n = fmaxf(n, 1e-12f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) g.q[k] = q[k] / n;
-    float x = opacity_raw[i] + a.opacity_bias;
+    float x = r.op;
     if (d) x = x + dl[13];
     g.op = 1.0f / (1.0f + act_expf(-x));
     g.drgb[0] = dl[10]; g.drgb[1] = dl[11]; g.drgb[2] = dl[12];
     return g;
+}
+__device__ __forceinline__ ActGaussian activate_vals(int i, const GvfGaussianActivation& a,
+                                                     const float* __restrict__ xyz_raw,
+                                                     const float* __restrict__ scaling_raw,
+                                                     const float* __restrict__ rotation_raw,
+                                                     const float* __restrict__ opacity_raw,
+                                                     const float (&dl)[14], bool d) {
+    return activate_finish(activate_raw(i, a, xyz_raw, scaling_raw, rotation_raw, opacity_raw), a, dl, d);
 }
 __device__ __forceinline__ ActGaussian activate_one(int i, const GvfGaussianActivation& a,
                                                     const float* __restrict__ xyz_raw,

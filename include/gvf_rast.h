@@ -242,7 +242,9 @@ int gvf_rast_profile_read(float* ms_sum /*[GVF_RAST_NSTAGES]*/, int* calls);
 /* How many gvf_rast_forward_batched() calls of this process took the shared-activation path: when the F frames of a call select few
  * distinct delta slices (the reference's render loop, utils/inference_utils.py:256-269: 128 cameras per timestep), the GaussianModel
  * activations (gaussian_model.py:84-114) and the 3-D covariances are computed once per (slice, Gaussian) instead of once per frame;
- * the outputs are the same bits either way (GVF_RAST_SHARED_ACT=0 in the environment forces the per-frame form).  A test aid. */
+ * the outputs are the same bits either way (GVF_RAST_SHARED_ACT=0 in the environment forces the per-frame form).  A test aid.
+ * The per-frame form of the bucket binning runs its projection launch with 64 Gaussians per workgroup and one frame per wave at a time;
+ * GVF_RAST_PRE_WAVE_FRAMES=0 in the environment (read per call) puts it on the 256-Gaussian mapping of the other paths: the same bits. */
 int64_t gvf_rast_shared_activation_calls(void);
 
 /* Diagnostic of the per-tile sort (R4): how many (frame, tile) segments of the LAST gvf_rast_forward*() call on this workspace fell into the
