@@ -60,6 +60,8 @@ SOURCES = {
     "interp.hip": ["-ffp-contract=off"],
     # fused clip + AdamW + EMA step: one rounding per written operation (the conformance bars count them)
     "optim.hip": ["-ffp-contract=off"],
+    # LayerNorm / gate / RMSNorm training kernels: default flags, as elem.hip (the backward recomputes the forward's row statistics)
+    "dit_train.hip": [],
 }
 
 

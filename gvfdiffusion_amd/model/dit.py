@@ -204,6 +204,7 @@ class DiT(nn.Module):
         self.compute_dtype = None # None: ops/precision.py decides per forward (GVF_DIT_DTYPE, autocast, use_fp16 -> fp16 else bf16)
         self._ctx_cache = {}      # step-invariant condition products
         self.use_graph = False    # replay the whole forward as one hipGraph (set by enable_graph)
+        self.train_forward = False  # forward() under grad = the differentiable forward (set by enable_training)
         import os
         # LayerNorm folded into the GEMMs (see _forward): 0 = off (default), 1 = every projection, 2 = only the narrow ones
         # (N <= 512).  Built, bit-checked (tests/test_dit_gpu.py::test_layernorm_folded_into_the_gemms) and measured on the
@@ -626,9 +627,23 @@ class DiT(nn.Module):
     # ---- forward ------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, t: torch.Tensor, cond_images: torch.Tensor, static_latent: torch.Tensor,
                 deformation_position_xyz: torch.Tensor = None) -> torch.Tensor:
+        if self.train_forward and torch.is_grad_enabled():
+            if self.use_graph:
+                raise RuntimeError("DiT: enable_training() and enable_graph() are both on -- a captured graph replays the inference launches and "
+                                   "carries no gradient; switch one of them off")
+            from . import dit_train
+            return dit_train.forward_train(self, x, t, cond_images, static_latent, deformation_position_xyz)
         if self.use_graph:
             return self._forward_graphed(x, t, cond_images, static_latent, deformation_position_xyz)
         return self._forward(x, t, cond_images, static_latent, deformation_position_xyz)
+
+    def enable_training(self, on: bool = True):
+        """With the switch on, forward() under enabled grad is the differentiable forward of model/dit_train.py (gradients to every parameter;
+        the element-wise hot path on the kernels of csrc/dit_train.hip, attention on csrc/attn_bwd.hip); under torch.no_grad() and with the
+        switch off (the default) it is the inference forward, unchanged.  Deliberately not keyed on module.training or requires_grad: both
+        are on by default and the inference path would change under its callers.  Not combinable with enable_graph()."""
+        self.train_forward = bool(on)
+        return self
 
     def enable_graph(self, on: bool = True):
         """Capture the ~200 launches of one forward pass into a hipGraph on first use and replay it for

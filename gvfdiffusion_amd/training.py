@@ -13,9 +13,12 @@ The interpolation ("deformation xyz") term of the same step (train_vae.py:304-31
 the static anchors, the weighted gather of their motion and the masked L1 against the predicted deltas as fused HIP kernels
 (ops/knn_interp.py: gvf_knn_interp_weights, gvf_interp_loss_forward / _backward), where the reference needs pytorch3d's knn_points.
 Attention trains through its HIP kernels: with grad enabled, model/attention/full_attn.py::scaled_dot_product_attention runs the
-inference forward inside an autograd function whose backward is csrc/attn_bwd.hip (ops/attention_grad.py), so a reference-style
-transformer block -- torch nn.Linear / LayerNorm / MultiHeadRMSNorm around that operator -- trains on this package; the projections
-and norms around it are torch's, and the fused GEMM / row-block kernels of the inference path carry no gradient.  `DeltaHead` is the
+inference forward inside an autograd function whose backward is csrc/attn_bwd.hip (ops/attention_grad.py).
+The DiT trains here too: `DiT.enable_training()` makes its forward the differentiable one of model/dit_train.py -- LayerNorm + adaLN
+modulate, the gated residual and the QK RMSNorm forward and backward as fused HIP kernels (ops/dit_train.py, csrc/dit_train.hip), attention on
+the operator above, the matrix products on torch's library GEMMs; the fused GEMM / row-block launches of the inference path still carry
+no gradient.  `diffusion_loss` is the loss of train_latent.py:183-207 on model/gaussian_diffusion.py::training_losses, ready for
+`train_step` with an ops.optim.FusedAdamW.  `DeltaHead` is the
 smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
 per-Gaussian features, producing the (T, P, 14) deltas.
 """
@@ -107,6 +110,24 @@ def interpolation_loss(static_gs: Sequence[torch.Tensor], micro_static_pc: torch
     loss, est = interpolation_l1(pred, q, micro_static_pc, micro_moving_pc, lengths=lengths, k=knn_k, beta=beta,
                                  adaptive_radius=adaptive_radius, return_est=True)
     return loss, {"deformation_xyz_loss": loss.detach().reshape(1)}, est
+
+
+def diffusion_loss(diffusion, model, latent: torch.Tensor, cond: dict, sampler=None, t: Optional[torch.Tensor] = None,
+                   noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The diffusion training loss of train_latent.py:183-207: t ~ sampler (model/resample.py; uniform over the diffusion's steps when
+    neither `sampler` nor `t` is given), losses = diffusion.training_losses(model, latent, t, model_kwargs=cond, noise), returns
+    losses["loss"].mean().  cond holds the model's keyword arguments (cond_images, static_latent, deformation_position_xyz); the
+    reference's `mem_ratio` entry (its elastic checkpointing ratio) is not accepted -- set use_checkpoint on the blocks instead.
+    The sampler's importance weights are 1 for the uniform sampler and, as in the reference, do not enter the loss."""
+    if "mem_ratio" in cond:
+        raise ValueError("diffusion_loss: 'mem_ratio' is not a model argument here (no elastic checkpointing); drop it from cond")
+    if t is None:
+        if sampler is None:
+            from .model.resample import UniformSampler
+            sampler = UniformSampler(diffusion.num_timesteps)
+        t, _ = sampler.sample(latent.shape[0], latent.device)
+    losses, _ = diffusion.training_losses(model, latent, t, model_kwargs=cond, noise=noise)
+    return losses["loss"].mean()
 
 
 def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20, flat=None) -> int:
