@@ -62,6 +62,8 @@ SOURCES = {
     "optim.hip": ["-ffp-contract=off"],
     # LayerNorm / gate / RMSNorm training kernels: default flags, as elem.hip (the backward recomputes the forward's row statistics)
     "dit_train.hip": [],
+    # weight gradient + transposing cast: the gemm.hip flags (accumulators in VGPRs: the epilogue stores them without accvgpr reads)
+    "linear_grad.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

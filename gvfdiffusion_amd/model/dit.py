@@ -205,6 +205,7 @@ class DiT(nn.Module):
         self._ctx_cache = {}      # step-invariant condition products
         self.use_graph = False    # replay the whole forward as one hipGraph (set by enable_graph)
         self.train_forward = False  # forward() under grad = the differentiable forward (set by enable_training)
+        self.train_linear = "torch" # route of the block projections in the differentiable forward (enable_training(linear=...))
         import os
         # LayerNorm folded into the GEMMs (see _forward): 0 = off (default), 1 = every projection, 2 = only the narrow ones
         # (N <= 512).  Built, bit-checked (tests/test_dit_gpu.py::test_layernorm_folded_into_the_gemms) and measured on the
@@ -632,17 +633,22 @@ class DiT(nn.Module):
                 raise RuntimeError("DiT: enable_training() and enable_graph() are both on -- a captured graph replays the inference launches and "
                                    "carries no gradient; switch one of them off")
             from . import dit_train
-            return dit_train.forward_train(self, x, t, cond_images, static_latent, deformation_position_xyz)
+            return dit_train.forward_train(self, x, t, cond_images, static_latent, deformation_position_xyz, linear=self.train_linear)
         if self.use_graph:
             return self._forward_graphed(x, t, cond_images, static_latent, deformation_position_xyz)
         return self._forward(x, t, cond_images, static_latent, deformation_position_xyz)
 
-    def enable_training(self, on: bool = True):
+    def enable_training(self, on: bool = True, linear: str = "torch"):
         """With the switch on, forward() under enabled grad is the differentiable forward of model/dit_train.py (gradients to every parameter;
         the element-wise hot path on the kernels of csrc/dit_train.hip, attention on csrc/attn_bwd.hip); under torch.no_grad() and with the
         switch off (the default) it is the inference forward, unchanged.  Deliberately not keyed on module.training or requires_grad: both
-        are on by default and the inference path would change under its callers.  Not combinable with enable_graph()."""
+        are on by default and the inference path would change under its callers.  Not combinable with enable_graph().
+        linear: the block projections' route, "torch" (the default: torch's library GEMM on per-step casts of the master weights) or "hip"
+        (forward, input, weight and bias gradients on this library's kernels, ops/linear_grad.py); anything else raises ValueError."""
+        if linear not in ("torch", "hip"):
+            raise ValueError(f"enable_training: linear must be 'torch' or 'hip', got {linear!r}")
         self.train_forward = bool(on)
+        self.train_linear = linear
         return self
 
     def enable_graph(self, on: bool = True):

@@ -6,14 +6,17 @@ Between two projections of a sub-layer the reference's composition is a chain of
 multiply, the shift add, the casts, the gate multiply, the residual add, F.normalize and the gain) and as many again in backward, plus the
 broadcast-gradient sums over the rows of a sample.  Here each chain is one operator of ops/dit_train.py: `layernorm_modulate` writes the 16-bit
 operand, `rmsnorm_heads` normalises q and k in place of the packed projection, `gate_residual` closes the sub-layer on the fp32 stream;
-attention is ops/attention_grad.py.  The matrix products are torch's library GEMMs (F.linear in the operand type on per-step casts of
-the fp32 master weights; the casts are differentiable, so the gradients arrive in fp32 on the parameters).  tanh-GELU is torch's.  What
-oracle/dit_ref.py lists as FP32_SITES of the inference path stays fp32 torch here too: input and final layer, timestep embedder, adaLN
-projections, condition projections.
+attention is ops/attention_grad.py.  The block projections (to_qkv, to_q, to_kv, to_out, mlp.0, mlp.2) take one of two routes, `linear=`:
+"torch" (the default) is torch's library GEMM -- F.linear in the operand type on per-step casts of the fp32 master weights; the casts are
+differentiable, so the gradients arrive on the parameters in fp32 after a 16-bit rounding -- and "hip" is ops/linear_grad.py: forward and input
+gradient on gvf_gemm, the weight and bias gradients in fp32 from csrc/linear_grad.hip, each weight cast (and transposed) once per step.
+tanh-GELU is torch's.  What oracle/dit_ref.py lists as FP32_SITES of the inference path stays fp32 torch here too: input and final layer,
+timestep embedder, adaLN projections, condition projections.
 
 `ops` is the seam through which the five operators are reached -- layernorm_modulate, gate_residual, rmsnorm_heads, attention, linear --
-as attributes of one object.  None means the HIP ones (HipOps); the product never substitutes anything else.  A test or a benchmark hands
-in a torch composition with the same signatures to check the wiring on the CPU or to time the baseline."""
+as attributes of one object.  None means the HIP ones (HipOps, or HipGemmOps for linear="hip"); the product never substitutes anything else.  A
+test or a benchmark hands in a torch composition with the same signatures to check the wiring on the CPU or to time the baseline.  An `ops`
+with a `linear_params(x, weight_fp32, bias_fp32, dtype)` attribute is handed the master parameters of a projection instead of their casts."""
 import torch
 import torch.nn.functional as F
 import torch.utils.checkpoint
@@ -50,8 +53,27 @@ class HipOps:
         return F.linear(x, weight, bias)
 
 
+class HipGemmOps(HipOps):
+    """HipOps with the block projections on this library's GEMMs (ops/linear_grad.py).  One instance per forward_train call: it owns the 16-bit
+    images of that call's weights, keyed by parameter, so every weight is cast once per step and a use_checkpoint recompute reads the same
+    images (and gives the same bits)."""
+
+    def __init__(self):
+        self.weight_images = {}
+
+    def linear_params(self, x, weight, bias, dtype):
+        from ..ops import linear_grad
+        return linear_grad.linear(x, weight, bias, dtype=dtype, cache=self.weight_images)
+
+
+LINEAR_ROUTES = ("torch", "hip")
+
+
 def _lin(ops, x, lin, lp):
-    """A projection in the operand type on casts of the fp32 master weights."""
+    """A projection in the operand type: on the fp32 master parameters where `ops` takes them, else on casts of them."""
+    linear_params = getattr(ops, "linear_params", None)
+    if linear_params is not None:
+        return linear_params(x, lin.weight, lin.bias, lp)
     return ops.linear(x, lin.weight.to(lp), None if lin.bias is None else lin.bias.to(lp))
 
 
@@ -103,14 +125,17 @@ def _block(ops, blk, lp, x, t_emb, image_emb, static_emb):
     return ops.gate_residual(x, _lin(ops, h, blk.mlp.mlp[2], lp), g_m, rpg)
 
 
-def forward_train(model, x, t, cond_images, static_latent, deformation_position_xyz=None, ops=None, dtype=None):
+def forward_train(model, x, t, cond_images, static_latent, deformation_position_xyz=None, ops=None, dtype=None, linear="torch"):
     """model: a gvfdiffusion_amd.model.dit.DiT; x [B, T, N, Cin], t [B] (float or integer steps), cond_images [B, T, Li, Ci],
     static_latent [B, Ls, Cs], deformation_position_xyz [B, N, 3] -> [B, T, N, out_channels] fp32 with a graph to every parameter.
     dtype: the 16-bit operand type; None resolves it as the inference forward does (ops/precision.py).  torch.float32 is accepted only
-    together with an `ops` of the caller's (the CPU check of the wiring)."""
+    together with an `ops` of the caller's (the CPU check of the wiring).  linear: the route of the block projections when `ops` is None,
+    "torch" (library GEMM) or "hip" (ops/linear_grad.py)."""
+    if linear not in LINEAR_ROUTES:
+        raise ValueError(f"forward_train: linear must be one of {LINEAR_ROUTES}, got {linear!r}")
     lp = dtype if dtype is not None else model._lp()
     if ops is None:
-        ops = HipOps
+        ops = HipGemmOps() if linear == "hip" else HipOps
         if lp not in precision.LP_DTYPES:
             raise ValueError(f"forward_train: the HIP operators take torch.float16 or torch.bfloat16 operands, got {lp}")
     B, T, N, _ = x.shape

@@ -16,8 +16,9 @@ Attention trains through its HIP kernels: with grad enabled, model/attention/ful
 inference forward inside an autograd function whose backward is csrc/attn_bwd.hip (ops/attention_grad.py).
 The DiT trains here too: `DiT.enable_training()` makes its forward the differentiable one of model/dit_train.py -- LayerNorm + adaLN
 modulate, the gated residual and the QK RMSNorm forward and backward as fused HIP kernels (ops/dit_train.py, csrc/dit_train.hip), attention on
-the operator above, the matrix products on torch's library GEMMs; the fused GEMM / row-block launches of the inference path still carry
-no gradient.  `diffusion_loss` is the loss of train_latent.py:183-207 on model/gaussian_diffusion.py::training_losses, ready for
+the operator above.  The block projections take torch's library GEMMs by default and, with `enable_training(linear="hip")`, this library's
+own: forward and input gradient on gvf_gemm, weight and bias gradients in fp32 from csrc/linear_grad.hip (ops/linear_grad.py), each weight
+cast once per step; the fused epilogues and row-block launches of the inference path still carry no gradient.  `diffusion_loss` is the loss of train_latent.py:183-207 on model/gaussian_diffusion.py::training_losses, ready for
 `train_step` with an ops.optim.FusedAdamW.  `DeltaHead` is the
 smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
 per-Gaussian features, producing the (T, P, 14) deltas.

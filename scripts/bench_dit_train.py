@@ -9,7 +9,13 @@ GPU only.
      optimizer step's 5.2 TB/s (profiles/r13_optim_step.txt).
   3. one full-size DiT forward + backward (tests/golden/dit_manifest.json = configs/diffusion.yml, B 1, T 24, N 512, seed-generated weights):
      the HIP operators; the torch element-wise operators around the HIP attention (isolates the three operators); torch everywhere
-     (scaled_dot_product_attention).
+     (scaled_dot_product_attention); and the HIP operators with linear="hip" (the block projections on this library's GEMMs,
+     ops/linear_grad.py), alternated with linear="torch" in the same process.
+  4. each block projection at the released shapes (C 512, M = 24 x 512; to_kv at M = 24 x 1370 and 24 x 4096): forward (gvf_gemm), input
+     gradient (gvf_gemm on the transposed image) and weight + bias gradient (gvf_gemm_wgrad) alone, time and TFLOP/s (2 M N K each), next to
+     torch's F.linear forward + backward on pre-cast 16-bit weights (the linear="torch" route without its casts); the weight gradient also over
+     a sweep of split counts; and the per-step cast_transpose over all block weights of the released model.
+GVF_BENCH_SECTIONS (default "ops,full,linear") selects the sections.
 Counted bytes per element (compulsory traffic: every row read or written once): LayerNorm fwd 6 (x 4, y 2) + bwd 10 (x 4, dy 2, dx 4);
 gate fwd 10 (x 4, h 2, out 4) + bwd 8 (dout 4, h 2, dh 2); RMSNorm fwd 4 + bwd 6."""
 import ctypes
@@ -33,6 +39,7 @@ dev = torch.device("cuda:0")
 N_STEPS = int(os.environ.get("GVF_STEPS", 20))
 ROUNDS = int(os.environ.get("GVF_ROUNDS", 3))
 FULL = os.environ.get("GVF_BENCH_FULL", "1") != "0"
+SECTIONS = set(os.environ.get("GVF_BENCH_SECTIONS", "ops,full,linear").split(","))
 C, H, D, TN = 512, 16, 32, 24 * 512
 HIP, TORCH = dit_train.HipOps, R.TorchOps()
 
@@ -141,14 +148,16 @@ def full_model():
         def attention(self, q, k, v):
             return HIP.attention(q, k, v)
 
-    def step(ops, dt):
+    def step(ops, dt, linear="torch"):
         def f():
             net.zero_grad(set_to_none=True)
-            y = dit_train.forward_train(net, inp["x"], inp["t"], inp["cond_images"], inp["static_latent"], inp["deformation_position_xyz"], ops=ops, dtype=dt)
+            y = dit_train.forward_train(net, inp["x"], inp["t"], inp["cond_images"], inp["static_latent"], inp["deformation_position_xyz"], ops=ops, dtype=dt,
+                                        linear=linear)
             ((y - target) ** 2).mean().backward()
         return f
     for dt, name in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
-        sides = {"hip operators": step(None, dt), "torch operators + hip attention": step(TorchAroundHipAttention(), dt),
+        sides = {"hip operators": step(None, dt), "hip operators, linear=hip": step(None, dt, "hip"),
+                 "torch operators + hip attention": step(TorchAroundHipAttention(), dt),
                  "torch operators + torch sdpa": step(R.TorchOps(attention="sdpa"), dt)}
         try:
             sides["torch operators + torch sdpa"]()
@@ -162,9 +171,56 @@ def full_model():
             print(f"  {k:34s} {span(v)} ms   ({min(v) / base:.2f} x the hip operators)")
 
 
+# (name, M, N, K) of the released model's block projections (C 512, B 1, T 24, N 512; 1370 image tokens, 4096 static tokens per frame)
+PROJECTIONS = [("to_qkv", TN, 1536, 512), ("to_out / to_q", TN, 512, 512), ("to_kv image", 24 * 1370, 1024, 512), ("to_kv static", 24 * 4096, 1024, 512),
+               ("mlp.0", TN, 2048, 512), ("mlp.2", TN, 512, 2048)]
+
+
+def linear_projections():
+    import torch.nn.functional as F
+    from gvfdiffusion_amd.ops import linear_grad
+    for dt, name in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+        print(f"block projections, {name}: ms (TFLOP/s at 2 M N K per product)")
+        for proj, M, N, K in PROJECTIONS:
+            g = torch.Generator(device=dev).manual_seed(M + N)
+            x = torch.randn((M, K), generator=g, device=dev).to(dt)
+            dy = torch.randn((M, N), generator=g, device=dev).to(dt)
+            w = torch.randn((N, K), generator=g, device=dev) / K ** 0.5
+            b = torch.randn((N,), generator=g, device=dev)
+            w16, w16t = linear_grad.cast_transpose(w, dt)
+            y, dx = torch.empty((M, N), dtype=dt, device=dev), torch.empty((M, K), dtype=dt, device=dev)
+            dw, db = torch.empty((N, K), device=dev), torch.empty((N,), device=dev)
+            auto = linear_grad.wgrad_splits(M, N, K)
+            ws = torch.empty(max(linear_grad.wgrad_workspace_bytes(M, N, K, s) for s in (auto, 2 * auto, 4 * auto)), dtype=torch.uint8, device=dev)
+            xt, wt, bt = x.clone().requires_grad_(), w16.clone().requires_grad_(), b.to(dt).requires_grad_()
+
+            def torch_fb():
+                xt.grad = wt.grad = bt.grad = None
+                F.linear(xt, wt, bt).backward(dy)
+            sides = {"forward": lambda: dit_ops.gemm(x, w16, b, y, dit_ops.EPI_STORE_16), "dgrad": lambda: dit_ops.gemm(dy, w16t, None, dx, dit_ops.EPI_STORE_16),
+                     "torch fwd+bwd": torch_fb}
+            cands = sorted({max(1, auto // 2), auto, 2 * auto, 4 * auto})
+            for s_ in cands:
+                sides[f"wgrad s={s_}"] = (lambda s_=s_: linear_grad.wgrad(dy, x, True, s_, out=dw, out_bias=db, workspace=ws))
+            res = alternate(sides)
+            fl = 2.0 * M * N * K
+            hip3 = min(res["forward"]) + min(res["dgrad"]) + min(res[f"wgrad s={auto}"])
+            print(f"  {proj:14s} M {M:6d} N {N:5d} K {K:5d}: " + "  ".join(f"{k} {span(v)} ({fl / min(v) / 1e9:.0f})" for k, v in res.items() if k != "torch fwd+bwd"))
+            print(f"  {'':14s} auto splits {auto}; forward + dgrad + wgrad {hip3:.3f} ms ({3 * fl / hip3 / 1e9:.0f} TFLOP/s)  torch F.linear fwd+bwd {span(res['torch fwd+bwd'])} ms "
+                  f"({3 * fl / min(res['torch fwd+bwd']) / 1e9:.0f} TFLOP/s)  torch / hip {min(res['torch fwd+bwd']) / hip3:.2f} x", flush=True)
+        man = json.load(open(os.path.join(ROOT, "tests", "golden", "dit_manifest.json")))
+        nb = int(man["config"]["num_blocks"])
+        shapes = [(1536, 512), (512, 512)] * 2 + [(512, 512), (1024, 512), (512, 512)] * 2 + [(2048, 512), (512, 2048)]
+        ws_ = [torch.randn(s, device=dev) for s in shapes]
+        t = timed(lambda: [linear_grad.cast_transpose(w_, dt) for w_ in ws_], N_STEPS)
+        n_el = sum(a * b_ for a, b_ in shapes)
+        print(f"  cast_transpose of one block's 12 weights ({n_el / 1e6:.2f} M elements, 8 bytes each counted): {t:.3f} ms = {8 * n_el / t / 1e9:.2f} TB/s; "
+              f"x {nb} blocks = {t * nb:.2f} ms per step", flush=True)
+
+
 def main():
     print(torch.cuda.get_device_name(0), _lib.lib().gvf_version().decode(), f"; {N_STEPS} steps x {ROUNDS} rounds, ms per call: min .. max of the rounds", flush=True)
-    for dt, name in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")):
+    for dt, name in ((torch.float16, "fp16"), (torch.bfloat16, "bf16")) if "ops" in SECTIONS else ():
         for B in (1, 4):
             print(f"operators forward + backward, rows = {B} x 24 x 512, C 512, H 16, d 32, {name}:")
             for op, (make, nbytes) in op_sides(B, dt).items():
@@ -175,7 +231,9 @@ def main():
             res = alternate(sides)
             for k, v in res.items():
                 print(f"  {k:20s} alone {span(v)} ms  {nb[k] / min(v) / 1e9:.2f} TB/s on {nb[k] / 1e6:.0f} MB counted (optimizer step: 5.2 TB/s)", flush=True)
-    if FULL:
+    if "linear" in SECTIONS:
+        linear_projections()
+    if FULL and "full" in SECTIONS:
         full_model()
 
 
