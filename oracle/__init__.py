@@ -2,7 +2,8 @@
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this package
 (never gvfdiffusion_amd/).  It wraps the plain-C restatements in this directory
-(rast_oracle.c, rast_bwd_oracle.c, vox2seq_oracle.c -> libgvf_oracle.so, built by `make -C oracle`) and holds the
+(rast_oracle.c, rast_bwd_oracle.c, vox2seq_oracle.c -> libgvf_oracle.so; rast_bwd_oracle.c in single precision ->
+libgvf_oracle_f32.so, the fp32 yardstick; both built by `make -C oracle`) and holds the
 torch-fp32 restatements of the floating-point DiT / sampler path (dit_ref.py, dpm_ref.py).
 """
 import ctypes
@@ -13,14 +14,16 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIB32 = None
 
 
 def build(force: bool = False) -> str:
     so = os.path.join(_HERE, "libgvf_oracle.so")
+    sos = (so, os.path.join(_HERE, "libgvf_oracle_f32.so"))
     srcs = [os.path.join(_HERE, f) for f in ("rast_oracle.c", "rast_bwd_oracle.c", "vox2seq_oracle.c", "Makefile")]
-    stale = (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)
+    stale = any((not os.path.exists(o)) or any(os.path.getmtime(s) > os.path.getmtime(o) for s in srcs) for o in sos)
     if force or stale:
-        subprocess.check_call(["make", "-C", _HERE, "-B", "libgvf_oracle.so"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", _HERE, "-B", "all"], stdout=subprocess.DEVNULL)
     return so
 
 
@@ -29,6 +32,15 @@ def lib():
     if _LIB is None:
         _LIB = ctypes.CDLL(build())
     return _LIB
+
+
+def lib32():
+    """The fp32 yardstick of the rasteriser backward (gvfo32_*)."""
+    global _LIB32
+    if _LIB32 is None:
+        build()
+        _LIB32 = ctypes.CDLL(os.path.join(_HERE, "libgvf_oracle_f32.so"))
+    return _LIB32
 
 
 def _f32(a):
@@ -200,3 +212,110 @@ def rast64_backward(means3D, shs, colors_precomp, opacities, scales, rotations, 
     assert rc == 0
     out.update(shs=g_shs, colors_precomp=g_col, scales=g_sc, rotations=g_ro, cov3D_precomp=g_c6)
     return out
+
+
+# ---- the backward in its two stages, in fp64 (the reference) and in fp32 (the yardstick: the same file compiled with real = float) ---
+class _Prec:
+    def __init__(self, dtype, ctype, getlib, prefix):
+        self.dtype, self.ctype, self.getlib, self.prefix = dtype, ctype, getlib, prefix
+
+    def fn(self, name):
+        return getattr(self.getlib(), self.prefix + name)
+
+    def arr(self, a):
+        return None if a is None else np.ascontiguousarray(a, dtype=self.dtype)
+
+    def ptr(self, a):
+        return None if a is None else a.ctypes.data_as(ctypes.POINTER(self.ctype))
+
+    def scene(self, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, H, W, tanfovx, tanfovy, kernel_size,
+              scale_modifier, mode, viewmatrix, projmatrix, campos, sh_degree, bg):
+        m3 = self.arr(means3D); P = m3.shape[0]
+        sh = self.arr(shs); M = 0 if sh is None else sh.shape[1]
+        keep = (m3, sh, self.arr(colors_precomp), self.arr(np.reshape(opacities, (-1,))), self.arr(scales), self.arr(rotations),
+                self.arr(cov3D_precomp), self.arr(np.reshape(viewmatrix, (-1,))), self.arr(np.reshape(projmatrix, (-1,))),
+                self.arr(campos), self.arr(bg))
+        r = self.ctype
+        args = [P, M, int(sh_degree)] + [self.ptr(a) for a in keep[:7]] + \
+               [int(H), int(W), r(tanfovx), r(tanfovy), r(kernel_size), r(scale_modifier), int(mode)] + [self.ptr(a) for a in keep[7:]]
+        return P, M, keep, args
+
+
+_P64 = _Prec(np.float64, ctypes.c_double, lib, "gvfo64_")
+_P32 = _Prec(np.float32, ctypes.c_float, lib32, "gvfo32_")
+_U8 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+_I32 = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+FLAG_NEAR, FLAG_CLAMPED, FLAG_VISIBLE = 1, 2, 4      # the per-Gaussian flag byte of chain() / project()
+
+
+def _accumulators(pr, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dalpha, dL_ddepth,
+                  subpixel_offset, scene_kw):
+    P, M, keep, args = pr.scene(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, **scene_kw)
+    so, gc, ga, gd = pr.arr(subpixel_offset), pr.arr(dL_dcolor), pr.arr(dL_dalpha), pr.arr(dL_ddepth)
+    acc, acc_abs = np.zeros((P, 10), pr.dtype), np.zeros((P, 10), pr.dtype)
+    radii, rects = np.zeros((P,), np.int32), np.zeros((P, 4), np.int32)
+    rc = pr.fn("accumulators")(*args, pr.ptr(so), pr.ptr(gc), pr.ptr(ga), pr.ptr(gd), pr.ptr(acc), pr.ptr(acc_abs), _I32(radii), _I32(rects))
+    assert rc == 0
+    return dict(acc=acc, acc_abs=acc_abs, radii=radii, rects=rects)
+
+
+def _chain(pr, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, scene_kw):
+    P, M, keep, args = pr.scene(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, **scene_kw)
+    acc = pr.arr(acc)
+    assert acc.shape == (P, 10)
+    z = lambda *s: np.zeros(s, pr.dtype)
+    out = dict(means3D=z(P, 3), means2D=z(P, 2), opacities=z(P), cov3D_precomp=z(P, 6),
+               shs=z(P, M, 3) if shs is not None else None, colors_precomp=z(P, 3) if colors_precomp is not None else None,
+               scales=z(P, 3) if cov3D_precomp is None else None, rotations=z(P, 4) if cov3D_precomp is None else None)
+    flags = np.zeros((P,), np.uint8)
+    rc = pr.fn("chain")(*args, pr.ptr(acc), *[pr.ptr(out[k]) for k in ("means3D", "means2D", "shs", "colors_precomp", "opacities", "scales",
+                                                                     "rotations", "cov3D_precomp")], _U8(flags))
+    assert rc == 0
+    out["flags"] = flags
+    return out
+
+
+def _project(pr, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, txty_fixed, scene_kw):
+    P, M, keep, args = pr.scene(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, **scene_kw)
+    fixed = pr.arr(txty_fixed)
+    out, txty, flags = np.zeros((P, 10), pr.dtype), np.zeros((P, 2), pr.dtype), np.zeros((P,), np.uint8)
+    rc = pr.fn("project")(*args, pr.ptr(fixed), pr.ptr(out), _U8(flags), pr.ptr(txty))
+    assert rc == 0
+    return dict(out=out, flags=flags, txty=txty)
+
+
+def rast64_accumulators(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dalpha=None,
+                        dL_ddepth=None, *, subpixel_offset=None, **scene_kw):
+    """Stage 1 of rast64_backward, the blend's backward: dict(acc[P,10], acc_abs[P,10], radii[P], rects[P,4]).  acc = d/d(x, y) [pixels],
+    d/d(conic a, b, c), d/d(opacity_eff), d/d(r, g, b), d/d(depth); acc_abs = the same sums over absolute per-(pixel, splat) terms.
+    scene_kw: the keyword arguments of rast64_backward.  subpixel_offset: (H, W, 2)."""
+    return _accumulators(_P64, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dalpha, dL_ddepth,
+                         subpixel_offset, scene_kw)
+
+
+def rast64_chain(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, **scene_kw):
+    """Stage 2 of rast64_backward, the per-Gaussian chain rule from given accumulators (linear in them): the dict of rast64_backward plus
+    flags[P] (uint8: FLAG_NEAR | FLAG_CLAMPED | FLAG_VISIBLE)."""
+    return _chain(_P64, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, scene_kw)
+
+
+def rast64_project(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, *, txty_fixed=None, **scene_kw):
+    """The per-Gaussian forward the chain rule differentiates: dict(out[P,10] = x, y, conic a, b, c, opacity_eff, r, g, b, depth,
+    flags[P], txty[P,2]).  txty_fixed: clamped view coordinates are held at these values (the chain rule gives them no gradient)."""
+    return _project(_P64, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, txty_fixed, scene_kw)
+
+
+def rast32_accumulators(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dalpha=None,
+                        dL_ddepth=None, *, subpixel_offset=None, **scene_kw):
+    """rast64_accumulators with every operation rounded to fp32: the yardstick."""
+    return _accumulators(_P32, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, dL_dcolor, dL_dalpha, dL_ddepth,
+                         subpixel_offset, scene_kw)
+
+
+def rast32_chain(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, *, mutant=0, **scene_kw):
+    """rast64_chain with every operation rounded to fp32: the yardstick.  mutant (test-only, 1..7): one line of the chain rule broken."""
+    lib32().gvfo32_set_mutant(int(mutant))
+    try:
+        return _chain(_P32, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, scene_kw)
+    finally:
+        lib32().gvfo32_set_mutant(0)

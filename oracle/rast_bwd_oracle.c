@@ -19,51 +19,79 @@
  *     coordinate gets no gradient, and the dependence of the clamp bound on tz is ignored;
  *   - the gradient of the screen-space mean is reported in NDC units (d/d(ndc) = d/d(pixel) * 0.5 * W resp. H),
  *     the quantity `screenspace_points.grad` holds upstream.
+ * The backward is exported in its two stages, split at the accumulators: gvfo64_accumulators() (the blend's backward) and gvfo64_chain()
+ * (the per-Gaussian chain rule, linear in the accumulators); gvfo64_backward() is their composition.  gvfo64_project() is the per-Gaussian
+ * forward whose derivative the chain rule is.  tests/test_rast_bwd_conformance_gpu.py holds the device against each stage separately.
  * mip mode: the opacity compensation coef = sqrt(det0 / (det1 + 1e-6) + 1e-6) is differentiated exactly.
  */
-#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <tgmath.h>
+
+/* One source, two builds.  Default: real = double, symbols gvfo64_* (the reference).  -DGVFO_F32 (with -fsingle-precision-constant and
+ * -ffp-contract=off): real = float, every operation and constant rounded to single precision, symbols gvfo32_* -- the "fp32 yardstick",
+ * the same formulas as a naive single-precision composition (what a correct fp32 kernel may be expected to reach).  tgmath.h picks
+ * sqrtf / expf / ... from the operand type.  -DGVFO_MUTANTS (yardstick build only): a test-only switch that breaks one line of the chain
+ * rule at a time, so that tests/test_rast_bwd_ref.py can show that the conformance bar catches each of them. */
+#ifdef GVFO_F32
+typedef float real;
+#define SYM(n) gvfo32_##n
+#else
+typedef double real;
+#define SYM(n) gvfo64_##n
+#endif
+
+#ifdef GVFO_MUTANTS
+static int g_mutant = 0;
+void SYM(set_mutant)(int m) { g_mutant = m; }
+#define MUT(k) (g_mutant == (k))
+#else
+#define MUT(k) 0
+#endif
+/* mutants: 1 SH view-direction term of means3D dropped; 2 db[6][2] 4z -> 2z; 3 tx, ty terms of dtz dropped; 4 clamp multipliers ignored;
+ * 5 depth path, y component dropped; 6 mip coefficient, dd1 term dropped; 7 first sign of gq[0] flipped */
 
 #define TILE 16
 #define MODE_MIP 0
 #define MODE_DILATE 1
 
-static const double SH_C0 = 0.28209479177387814;
-static const double SH_C1 = 0.4886025119029199;
-static const double SH_C2[5] = {1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792,
+static const real SH_C0 = 0.28209479177387814;
+static const real SH_C1 = 0.4886025119029199;
+static const real SH_C2[5] = {1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792,
                                 0.5462742152960396};
-static const double SH_C3[7] = {-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154,
+static const real SH_C3[7] = {-0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154,
                                 -0.4570457994644658, 1.445305721320277, -0.5900435899266435};
 
 typedef struct {
     int visible;
-    double depth, x, y, ca, cb, cc, op, rgb[3];
+    real depth, x, y, ca, cb, cc, op, rgb[3];
     int x0, y0, x1, y1;
     /* intermediates kept for the backward pass */
-    double pv[3], c6[6], A0[3], A1[3], cxx, cxy, cyy; /* cxx.. BEFORE the filter */
-    double coef, tx, ty, tz, xmul, ymul, pw, ph[4];
+    real pv[3], c6[6], A0[3], A1[3], cxx, cxy, cyy; /* cxx.. BEFORE the filter */
+    real coef, tx, ty, tz, xmul, ymul, pw, ph[4];
     int clamped[3];
-    double dir[3], dlen;
+    int rad, flag;            /* integer 3-sigma radius; FLAG_* bits below */
+    real dir[3], dlen;
 } G64;
 
 typedef struct {
     int P, M, deg, H, W, mode;
-    const double *means3D, *shs, *colors_precomp, *opac, *scales, *rots, *cov3D;
-    double tanfovx, tanfovy, kernel_size, scale_mod;
-    const double *view, *proj, *campos, *bg;
+    const real *means3D, *shs, *colors_precomp, *opac, *scales, *rots, *cov3D;
+    real tanfovx, tanfovy, kernel_size, scale_mod;
+    const real *view, *proj, *campos, *bg;
+    const real* txty_fixed;   /* project() only: clamped view coordinates held at these values (the "no gradient" convention) */
 } Scene;
 
-static void cov3d(const double* s, double mod, const double* q, double* c6) {
-    double sx = mod * s[0], sy = mod * s[1], sz = mod * s[2];
-    double r = q[0], x = q[1], y = q[2], z = q[3];
-    double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
+static void cov3d(const real* s, real mod, const real* q, real* c6) {
+    real sx = mod * s[0], sy = mod * s[1], sz = mod * s[2];
+    real r = q[0], x = q[1], y = q[2], z = q[3];
+    real R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
                       {2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)},
                       {2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)}};
-    double sc[3] = {sx, sy, sz}, L[3][3];
+    real sc[3] = {sx, sy, sz}, L[3][3];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) L[i][j] = R[i][j] * sc[j];
-    double S[3][3];
+    real S[3][3];
     for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
         S[i][j] = 0;
         for (int k = 0; k < 3; ++k) S[i][j] += L[i][k] * L[j][k];
@@ -72,12 +100,12 @@ static void cov3d(const double* s, double mod, const double* q, double* c6) {
 }
 
 /* SH basis values b[16] for direction (x,y,z) */
-static void sh_basis(int deg, double x, double y, double z, double* b) {
+static void sh_basis(int deg, real x, real y, real z, real* b) {
     b[0] = SH_C0;
     if (deg > 0) {
         b[1] = -SH_C1 * y; b[2] = SH_C1 * z; b[3] = -SH_C1 * x;
         if (deg > 1) {
-            double xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+            real xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
             b[4] = SH_C2[0] * xy; b[5] = SH_C2[1] * yz; b[6] = SH_C2[2] * (2 * zz - xx - yy); b[7] = SH_C2[3] * xz;
             b[8] = SH_C2[4] * (xx - yy);
             if (deg > 2) {
@@ -89,18 +117,18 @@ static void sh_basis(int deg, double x, double y, double z, double* b) {
     }
 }
 /* d basis / d(x,y,z): db[k][3] */
-static void sh_basis_grad(int deg, double x, double y, double z, double db[16][3]) {
-    memset(db, 0, sizeof(double) * 48);
+static void sh_basis_grad(int deg, real x, real y, real z, real db[16][3]) {
+    memset(db, 0, sizeof(real) * 48);
     if (deg > 0) {
         db[1][1] = -SH_C1; db[2][2] = SH_C1; db[3][0] = -SH_C1;
         if (deg > 1) {
             db[4][0] = SH_C2[0] * y; db[4][1] = SH_C2[0] * x;
             db[5][1] = SH_C2[1] * z; db[5][2] = SH_C2[1] * y;
-            db[6][0] = SH_C2[2] * -2 * x; db[6][1] = SH_C2[2] * -2 * y; db[6][2] = SH_C2[2] * 4 * z;
+            db[6][0] = SH_C2[2] * -2 * x; db[6][1] = SH_C2[2] * -2 * y; db[6][2] = SH_C2[2] * (MUT(2) ? 2 : 4) * z;
             db[7][0] = SH_C2[3] * z; db[7][2] = SH_C2[3] * x;
             db[8][0] = SH_C2[4] * 2 * x; db[8][1] = SH_C2[4] * -2 * y;
             if (deg > 2) {
-                double xx = x * x, yy = y * y, zz = z * z;
+                real xx = x * x, yy = y * y, zz = z * z;
                 db[9][0] = SH_C3[0] * 6 * x * y; db[9][1] = SH_C3[0] * (3 * xx - 3 * yy);
                 db[10][0] = SH_C3[1] * y * z; db[10][1] = SH_C3[1] * x * z; db[10][2] = SH_C3[1] * x * y;
                 db[11][0] = SH_C3[2] * -2 * x * y; db[11][1] = SH_C3[2] * (4 * zz - xx - 3 * yy); db[11][2] = SH_C3[2] * 8 * y * z;
@@ -113,41 +141,54 @@ static void sh_basis_grad(int deg, double x, double y, double z, double db[16][3
     }
 }
 
+/* per-Gaussian flag byte of chain() / project() */
+#define FLAG_NEAR    1   /* an input comparison of the chain rule sits within 1e-5 (relative) of its threshold: pv.z vs 0.2, |tx/tz| or |ty/tz| vs
+                            1.3 tan(fov), an rgb channel vs the 0 clamp, mip det0 / det1 vs 1e-6 */
+#define FLAG_CLAMPED 2   /* visible, and tx or ty is clamped (xmul or ymul is 0) */
+#define FLAG_VISIBLE 4
+static int near_thr(real v, real thr) { return fabs(v - thr) <= (real)1e-5 * fabs(thr); }
+
 static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
 
 static void pre_one(const Scene* s, int i, G64* g) {
     memset(g, 0, sizeof(*g));
-    const double* p = s->means3D + 3 * (size_t)i;
-    const double* m = s->view;
+    const real* p = s->means3D + 3 * (size_t)i;
+    const real* m = s->view;
     g->pv[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
     g->pv[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
     g->pv[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
+    if (near_thr(g->pv[2], 0.2)) g->flag |= FLAG_NEAR;
     if (g->pv[2] <= 0.2) return;
     m = s->proj;
     for (int k = 0; k < 4; ++k) g->ph[k] = m[k] * p[0] + m[4 + k] * p[1] + m[8 + k] * p[2] + m[12 + k];
     g->pw = 1.0 / (g->ph[3] + 0.0000001);
-    double projx = g->ph[0] * g->pw, projy = g->ph[1] * g->pw;
-    if (s->cov3D) memcpy(g->c6, s->cov3D + 6 * (size_t)i, 6 * sizeof(double));
+    real projx = g->ph[0] * g->pw, projy = g->ph[1] * g->pw;
+    if (s->cov3D) memcpy(g->c6, s->cov3D + 6 * (size_t)i, 6 * sizeof(real));
     else cov3d(s->scales + 3 * (size_t)i, s->scale_mod, s->rots + 4 * (size_t)i, g->c6);
     int H = s->H, W = s->W;
-    double fx = (double)W / (2.0 * s->tanfovx), fy = (double)H / (2.0 * s->tanfovy);
-    double limx = 1.3 * s->tanfovx, limy = 1.3 * s->tanfovy;
-    double txtz = g->pv[0] / g->pv[2], tytz = g->pv[1] / g->pv[2];
+    real fx = (real)W / (2.0 * s->tanfovx), fy = (real)H / (2.0 * s->tanfovy);
+    real limx = 1.3 * s->tanfovx, limy = 1.3 * s->tanfovy;
+    real txtz = g->pv[0] / g->pv[2], tytz = g->pv[1] / g->pv[2];
     g->xmul = (txtz < -limx || txtz > limx) ? 0.0 : 1.0;
     g->ymul = (tytz < -limy || tytz > limy) ? 0.0 : 1.0;
+    if (near_thr(fabs(txtz), limx) || near_thr(fabs(tytz), limy)) g->flag |= FLAG_NEAR;
     g->tx = fmin(limx, fmax(-limx, txtz)) * g->pv[2];
     g->ty = fmin(limy, fmax(-limy, tytz)) * g->pv[2];
+    if (s->txty_fixed) {
+        if (g->xmul == 0.0) g->tx = s->txty_fixed[2 * (size_t)i];
+        if (g->ymul == 0.0) g->ty = s->txty_fixed[2 * (size_t)i + 1];
+    }
     g->tz = g->pv[2];
-    double J00 = fx / g->tz, J02 = -(fx * g->tx) / (g->tz * g->tz), J11 = fy / g->tz, J12 = -(fy * g->ty) / (g->tz * g->tz);
+    real J00 = fx / g->tz, J02 = -(fx * g->tx) / (g->tz * g->tz), J11 = fy / g->tz, J12 = -(fy * g->ty) / (g->tz * g->tz);
     for (int c = 0; c < 3; ++c) {
-        double w0 = s->view[c * 4 + 0], w1 = s->view[c * 4 + 1], w2 = s->view[c * 4 + 2];
+        real w0 = s->view[c * 4 + 0], w1 = s->view[c * 4 + 1], w2 = s->view[c * 4 + 2];
         g->A0[c] = J00 * w0 + J02 * w2;
         g->A1[c] = J11 * w1 + J12 * w2;
     }
-    const double* c6 = g->c6;
-    double S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-    double B0[3], B1[3];
+    const real* c6 = g->c6;
+    real S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
+    real B0[3], B1[3];
     for (int c = 0; c < 3; ++c) {
         B0[c] = g->A0[0] * S[0][c] + g->A0[1] * S[1][c] + g->A0[2] * S[2][c];
         B1[c] = g->A1[0] * S[0][c] + g->A1[1] * S[1][c] + g->A1[2] * S[2][c];
@@ -155,43 +196,46 @@ static void pre_one(const Scene* s, int i, G64* g) {
     g->cxx = B0[0] * g->A0[0] + B0[1] * g->A0[1] + B0[2] * g->A0[2];
     g->cxy = B0[0] * g->A1[0] + B0[1] * g->A1[1] + B0[2] * g->A1[2];
     g->cyy = B1[0] * g->A1[0] + B1[1] * g->A1[1] + B1[2] * g->A1[2];
-    double cxx = g->cxx, cxy = g->cxy, cyy = g->cyy, k = s->mode == MODE_MIP ? s->kernel_size : 0.3;
+    real cxx = g->cxx, cxy = g->cxy, cyy = g->cyy, k = s->mode == MODE_MIP ? s->kernel_size : 0.3;
     g->coef = 1.0;
     if (s->mode == MODE_MIP) {
-        double det0 = fmax(1e-6, cxx * cyy - cxy * cxy);
-        double det1 = fmax(1e-6, (cxx + k) * (cyy + k) - cxy * cxy);
+        if (near_thr(cxx * cyy - cxy * cxy, 1e-6) || near_thr((cxx + k) * (cyy + k) - cxy * cxy, 1e-6)) g->flag |= FLAG_NEAR;
+        real det0 = fmax(1e-6, cxx * cyy - cxy * cxy);
+        real det1 = fmax(1e-6, (cxx + k) * (cyy + k) - cxy * cxy);
         g->coef = sqrt(det0 / (det1 + 1e-6) + 1e-6);
         if (det0 <= 1e-6 || det1 <= 1e-6) g->coef = 0.0;
     }
     cxx += k; cyy += k;
-    double det = cxx * cyy - cxy * cxy;
+    real det = cxx * cyy - cxy * cxy;
     if (det == 0.0) return;
     g->ca = cyy / det; g->cb = -cxy / det; g->cc = cxx / det;
-    double mid = 0.5 * (cxx + cyy);
-    double lam1 = mid + sqrt(fmax(0.1, mid * mid - det)), lam2 = mid - sqrt(fmax(0.1, mid * mid - det));
-    double rad = ceil(3.0 * sqrt(fmax(lam1, lam2)));
-    g->x = ((projx + 1.0) * (double)W - 1.0) * 0.5;
-    g->y = ((projy + 1.0) * (double)H - 1.0) * 0.5;
+    real mid = 0.5 * (cxx + cyy);
+    real lam1 = mid + sqrt(fmax(0.1, mid * mid - det)), lam2 = mid - sqrt(fmax(0.1, mid * mid - det));
+    real rad = ceil(3.0 * sqrt(fmax(lam1, lam2)));
+    g->rad = (int)rad;
+    g->x = ((projx + 1.0) * (real)W - 1.0) * 0.5;
+    g->y = ((projy + 1.0) * (real)H - 1.0) * 0.5;
     int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    g->x0 = imin(gx, imax(0, (int)((g->x - rad) / (double)TILE)));
-    g->y0 = imin(gy, imax(0, (int)((g->y - rad) / (double)TILE)));
-    g->x1 = imin(gx, imax(0, (int)((g->x + rad + (double)(TILE - 1)) / (double)TILE)));
-    g->y1 = imin(gy, imax(0, (int)((g->y + rad + (double)(TILE - 1)) / (double)TILE)));
+    g->x0 = imin(gx, imax(0, (int)((g->x - rad) / (real)TILE)));
+    g->y0 = imin(gy, imax(0, (int)((g->y - rad) / (real)TILE)));
+    g->x1 = imin(gx, imax(0, (int)((g->x + rad + (real)(TILE - 1)) / (real)TILE)));
+    g->y1 = imin(gy, imax(0, (int)((g->y + rad + (real)(TILE - 1)) / (real)TILE)));
     if ((g->x1 - g->x0) * (g->y1 - g->y0) == 0) return;
     if (s->colors_precomp) {
         for (int c = 0; c < 3; ++c) g->rgb[c] = s->colors_precomp[3 * (size_t)i + c];
     } else {
-        double d[3] = {p[0] - s->campos[0], p[1] - s->campos[1], p[2] - s->campos[2]};
+        real d[3] = {p[0] - s->campos[0], p[1] - s->campos[1], p[2] - s->campos[2]};
         g->dlen = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
         for (int c = 0; c < 3; ++c) g->dir[c] = d[c] / g->dlen;
-        double b[16];
+        real b[16];
         sh_basis(s->deg, g->dir[0], g->dir[1], g->dir[2], b);
         int nb = (s->deg + 1) * (s->deg + 1);
-        const double* sh = s->shs + (size_t)i * s->M * 3;
+        const real* sh = s->shs + (size_t)i * s->M * 3;
         for (int c = 0; c < 3; ++c) {
-            double r = 0;
-            for (int kk = 0; kk < nb; ++kk) r += b[kk] * sh[kk * 3 + c];
+            real r = 0, mag = 0.5;
+            for (int kk = 0; kk < nb; ++kk) { r += b[kk] * sh[kk * 3 + c]; mag += fabs(b[kk] * sh[kk * 3 + c]); }
             r += 0.5;
+            if (fabs(r) <= (real)1e-5 * mag) g->flag |= FLAG_NEAR;
             g->clamped[c] = r < 0.0;
             g->rgb[c] = r < 0.0 ? 0.0 : r;
         }
@@ -199,9 +243,10 @@ static void pre_one(const Scene* s, int i, G64* g) {
     g->depth = g->pv[2];
     g->op = s->opac[i] * g->coef;
     g->visible = 1;
+    g->flag |= FLAG_VISIBLE | ((g->xmul == 0.0 || g->ymul == 0.0) ? FLAG_CLAMPED : 0);
 }
 
-typedef struct { double depth; int id; } DI;
+typedef struct { real depth; int id; } DI;
 static int di_cmp(const void* a, const void* b) {
     const DI* x = (const DI*)a; const DI* y = (const DI*)b;
     /* the device orders by the float32 depth bits, then by id */
@@ -219,21 +264,21 @@ static int pixel_list(const G64* g, int P, int px, int py, DI* list) {
     return n;
 }
 
-static void make_scene(Scene* s, int P, int M, int deg, const double* means3D, const double* shs, const double* colors_precomp,
-                       const double* opac, const double* scales, const double* rots, const double* cov3D, int H, int W,
-                       double tanfovx, double tanfovy, double kernel_size, double scale_mod, int mode, const double* view,
-                       const double* proj, const double* campos, const double* bg) {
+static void make_scene(Scene* s, int P, int M, int deg, const real* means3D, const real* shs, const real* colors_precomp,
+                       const real* opac, const real* scales, const real* rots, const real* cov3D, int H, int W,
+                       real tanfovx, real tanfovy, real kernel_size, real scale_mod, int mode, const real* view,
+                       const real* proj, const real* campos, const real* bg) {
     s->P = P; s->M = M; s->deg = deg; s->H = H; s->W = W; s->mode = mode;
     s->means3D = means3D; s->shs = shs; s->colors_precomp = colors_precomp; s->opac = opac; s->scales = scales; s->rots = rots;
     s->cov3D = cov3D; s->tanfovx = tanfovx; s->tanfovy = tanfovy; s->kernel_size = kernel_size; s->scale_mod = scale_mod;
-    s->view = view; s->proj = proj; s->campos = campos; s->bg = bg;
+    s->view = view; s->proj = proj; s->campos = campos; s->bg = bg; s->txty_fixed = NULL;
 }
 
-int gvfo64_forward(int P, int M, int deg, const double* means3D, const double* shs, const double* colors_precomp,
-                   const double* opac, const double* scales, const double* rots, const double* cov3D, int H, int W,
-                   double tanfovx, double tanfovy, double kernel_size, double scale_mod, int mode, const double* view,
-                   const double* proj, const double* campos, const double* bg, double* out_color, double* out_alpha,
-                   double* out_depth) {
+int SYM(forward)(int P, int M, int deg, const real* means3D, const real* shs, const real* colors_precomp,
+                   const real* opac, const real* scales, const real* rots, const real* cov3D, int H, int W,
+                   real tanfovx, real tanfovy, real kernel_size, real scale_mod, int mode, const real* view,
+                   const real* proj, const real* campos, const real* bg, real* out_color, real* out_alpha,
+                   real* out_depth) {
     Scene s;
     make_scene(&s, P, M, deg, means3D, shs, colors_precomp, opac, scales, rots, cov3D, H, W, tanfovx, tanfovy, kernel_size,
                scale_mod, mode, view, proj, campos, bg);
@@ -243,15 +288,15 @@ int gvfo64_forward(int P, int M, int deg, const double* means3D, const double* s
     for (int py = 0; py < H; ++py)
         for (int px = 0; px < W; ++px) {
             int n = pixel_list(g, P, px, py, list);
-            double T = 1.0, C[3] = {0, 0, 0}, D = 0;
+            real T = 1.0, C[3] = {0, 0, 0}, D = 0;
             for (int k = 0; k < n; ++k) {
                 const G64* q = &g[list[k].id];
-                double dx = q->x - (double)px, dy = q->y - (double)py;
-                double power = -0.5 * (q->ca * dx * dx + q->cc * dy * dy) - q->cb * dx * dy;
+                real dx = q->x - (real)px, dy = q->y - (real)py;
+                real power = -0.5 * (q->ca * dx * dx + q->cc * dy * dy) - q->cb * dx * dy;
                 if (power > 0.0) continue;
-                double alpha = fmin(0.99, q->op * exp(power));
+                real alpha = fmin(0.99, q->op * exp(power));
                 if (alpha < 1.0 / 255.0) continue;
-                double test_T = T * (1.0 - alpha);
+                real test_T = T * (1.0 - alpha);
                 if (test_T < 0.0001) break;
                 for (int c = 0; c < 3; ++c) C[c] += q->rgb[c] * alpha * T;
                 D += q->depth * alpha * T;
@@ -266,196 +311,262 @@ int gvfo64_forward(int P, int M, int deg, const double* means3D, const double* s
     return 0;
 }
 
-/* Gradients of  L = sum(dL_dcolor * color) + sum(dL_dalpha * alpha) + sum(dL_ddepth * depth)  w.r.t. every input.
- * Outputs may be NULL.  g_means2D[P][2]: NDC convention (see header). */
-int gvfo64_backward(int P, int M, int deg, const double* means3D, const double* shs, const double* colors_precomp,
-                    const double* opac, const double* scales, const double* rots, const double* cov3D, int H, int W,
-                    double tanfovx, double tanfovy, double kernel_size, double scale_mod, int mode, const double* view,
-                    const double* proj, const double* campos, const double* bg, const double* dL_dcolor,
-                    const double* dL_dalpha, const double* dL_ddepth, double* g_means3D, double* g_means2D, double* g_shs,
-                    double* g_colors, double* g_opac, double* g_scales, double* g_rots, double* g_cov3D) {
+#define SCENE_PARAMS                                                                                                          \
+    int P, int M, int deg, const real *means3D, const real *shs, const real *colors_precomp, const real *opac, const real *scales, \
+        const real *rots, const real *cov3D, int H, int W, real tanfovx, real tanfovy, real kernel_size, real scale_mod, int mode, \
+        const real *view, const real *proj, const real *campos, const real *bg
+#define SCENE_ARGS                                                                                                                   \
+    P, M, deg, means3D, shs, colors_precomp, opac, scales, rots, cov3D, H, W, tanfovx, tanfovy, kernel_size, scale_mod, mode, view, \
+        proj, campos, bg
+
+/* The oracle's per-Gaussian forward: out[P][10] = x, y [pixels], conic a, b, c, opacity_eff, r, g, b, depth -- the quantities the blend
+ * reads, in the order of the accumulators; zeros for an invisible Gaussian.  out_flag[P]: FLAG_* bits.  out_txty[P][2] (may be NULL): the
+ * view coordinates after the clamp.  txty_fixed (may be NULL): clamped coordinates are held at these values instead of 1.3 tan(fov) tz,
+ * which is the function whose derivative the chain rule reports ("a clamped coordinate gets no gradient"). */
+int SYM(project)(SCENE_PARAMS, const real* txty_fixed, real* out, uint8_t* out_flag, real* out_txty) {
     Scene s;
-    make_scene(&s, P, M, deg, means3D, shs, colors_precomp, opac, scales, rots, cov3D, H, W, tanfovx, tanfovy, kernel_size,
-               scale_mod, mode, view, proj, campos, bg);
+    make_scene(&s, SCENE_ARGS);
+    s.txty_fixed = txty_fixed;
+    for (int i = 0; i < P; ++i) {
+        G64 g;
+        pre_one(&s, i, &g);
+        real* o = out + 10 * (size_t)i;
+        for (int k = 0; k < 10; ++k) o[k] = 0;
+        if (g.visible) {
+            o[0] = g.x; o[1] = g.y; o[2] = g.ca; o[3] = g.cb; o[4] = g.cc; o[5] = g.op;
+            o[6] = g.rgb[0]; o[7] = g.rgb[1]; o[8] = g.rgb[2]; o[9] = g.depth;
+        }
+        if (out_flag) out_flag[i] = (uint8_t)g.flag;
+        if (out_txty) { out_txty[2 * (size_t)i] = g.tx; out_txty[2 * (size_t)i + 1] = g.ty; }
+    }
+    return 0;
+}
+
+/* Stage 1, the blend's backward.  acc[P][10] = d/d(x, y) [pixels], d/d(conic a, b, c), d/d(opacity_eff), d/d(r, g, b), d/d(depth) of
+ * L = sum(dL_dcolor * color) + sum(dL_dalpha * alpha) + sum(dL_ddepth * depth): the convention of the device's BWD_ACC.  acc_abs (may be
+ * NULL): the same sums with every per-(pixel, splat) term replaced by its absolute value (the scale of the rounding error of any
+ * summation order).  subpixel_offset[H*W][2] (may be NULL) moves each pixel's sample point.  out_radii[P] (may be NULL): the integer
+ * 3-sigma radius of a visible Gaussian, else 0; out_rects[P][4] (may be NULL): its tile rectangle x0, y0, x1, y1. */
+int SYM(accumulators)(SCENE_PARAMS, const real* subpixel_offset, const real* dL_dcolor, const real* dL_dalpha, const real* dL_ddepth,
+                      real* acc, real* acc_abs, int32_t* out_radii, int32_t* out_rects) {
+    Scene s;
+    make_scene(&s, SCENE_ARGS);
     size_t Pn = (size_t)(P > 0 ? P : 1);
     G64* g = (G64*)malloc(sizeof(G64) * Pn);
     DI* list = (DI*)malloc(sizeof(DI) * Pn);
-    /* accumulators of the blend's backward: d/d(x,y) [pixels], d/d(conic a,b,c) [true derivatives], d/d(op), d/d(rgb), d/d(depth) */
-    double* acc = (double*)calloc(Pn * 10, sizeof(double));
-    double* alphas = (double*)malloc(sizeof(double) * Pn);
-    double* Gs = (double*)malloc(sizeof(double) * Pn);
+    real* alphas = (real*)malloc(sizeof(real) * Pn);
+    real* Gs = (real*)malloc(sizeof(real) * Pn);
     int* used = (int*)malloc(sizeof(int) * Pn);
-    for (int i = 0; i < P; ++i) pre_one(&s, i, &g[i]);
+    memset(acc, 0, sizeof(real) * 10 * (size_t)P);
+    if (acc_abs) memset(acc_abs, 0, sizeof(real) * 10 * (size_t)P);
+    for (int i = 0; i < P; ++i) {
+        pre_one(&s, i, &g[i]);
+        if (out_radii) out_radii[i] = g[i].visible ? g[i].rad : 0;
+        if (out_rects) {
+            int32_t* r = out_rects + 4 * (size_t)i;
+            r[0] = g[i].visible ? g[i].x0 : 0; r[1] = g[i].visible ? g[i].y0 : 0;
+            r[2] = g[i].visible ? g[i].x1 : 0; r[3] = g[i].visible ? g[i].y1 : 0;
+        }
+    }
     for (int py = 0; py < H; ++py)
         for (int px = 0; px < W; ++px) {
             int n = pixel_list(g, P, px, py, list);
             size_t pid = (size_t)py * W + px;
+            real pxf = (real)px, pyf = (real)py;
+            if (subpixel_offset) { pxf += subpixel_offset[2 * pid]; pyf += subpixel_offset[2 * pid + 1]; }
             /* channels: r, g, b, depth, one (alpha_out = sum alpha_k T_k) with backgrounds bg, 0, 0 */
-            double dch[5] = {dL_dcolor[pid], dL_dcolor[(size_t)H * W + pid], dL_dcolor[(size_t)2 * H * W + pid],
-                             dL_ddepth ? dL_ddepth[pid] : 0.0, dL_dalpha ? dL_dalpha[pid] : 0.0};
-            double bgc[5] = {bg[0], bg[1], bg[2], 0.0, 0.0};
+            real dch[5] = {dL_dcolor[pid], dL_dcolor[(size_t)H * W + pid], dL_dcolor[(size_t)2 * H * W + pid],
+                           dL_ddepth ? dL_ddepth[pid] : (real)0.0, dL_dalpha ? dL_dalpha[pid] : (real)0.0};
+            real bgc[5] = {bg[0], bg[1], bg[2], 0.0, 0.0};
             /* forward replay */
-            double T = 1.0;
+            real T = 1.0;
             int m = 0;
             for (int k = 0; k < n; ++k) {
                 const G64* q = &g[list[k].id];
-                double dx = q->x - (double)px, dy = q->y - (double)py;
-                double power = -0.5 * (q->ca * dx * dx + q->cc * dy * dy) - q->cb * dx * dy;
+                real dx = q->x - pxf, dy = q->y - pyf;
+                real power = -0.5 * (q->ca * dx * dx + q->cc * dy * dy) - q->cb * dx * dy;
                 if (power > 0.0) continue;
-                double Gv = exp(power);
-                double alpha = fmin(0.99, q->op * Gv);
+                real Gv = exp(power);
+                real alpha = fmin(0.99, q->op * Gv);
                 if (alpha < 1.0 / 255.0) continue;
-                double test_T = T * (1.0 - alpha);
+                real test_T = T * (1.0 - alpha);
                 if (test_T < 0.0001) break;
                 used[m] = list[k].id; alphas[m] = alpha; Gs[m] = Gv; ++m;
                 T = test_T;
             }
-            const double T_final = T;
+            const real T_final = T;
             /* back to front.  suffix[ch] = sum_{j>k} c_j alpha_j T_j + T_final bg  (what lies behind splat k) */
-            double suffix[5];
+            real suffix[5];
             for (int ch = 0; ch < 5; ++ch) suffix[ch] = T_final * bgc[ch];
             for (int k = m - 1; k >= 0; --k) {
                 const int id = used[k];
                 const G64* q = &g[id];
-                const double alpha = alphas[k];
+                const real alpha = alphas[k];
                 T = T / (1.0 - alpha);                 /* transmittance in front of splat k */
-                double cch[5] = {q->rgb[0], q->rgb[1], q->rgb[2], q->depth, 1.0};
-                double dL_dalpha_k = 0.0;
+                real cch[5] = {q->rgb[0], q->rgb[1], q->rgb[2], q->depth, 1.0};
+                real dL_dalpha_k = 0.0, abs_dalpha_k = 0.0;
                 for (int ch = 0; ch < 5; ++ch) {
                     /* out = ... + c_k alpha T + (1 - alpha) * [behind / (1 - alpha)] : d out / d alpha = c_k T - suffix / (1 - alpha) */
                     dL_dalpha_k += (cch[ch] * T - suffix[ch] / (1.0 - alpha)) * dch[ch];
+                    if (acc_abs) abs_dalpha_k += (fabs(cch[ch] * T) + fabs(suffix[ch] / (1.0 - alpha))) * fabs(dch[ch]);
                     suffix[ch] += cch[ch] * alpha * T;
                 }
-                double* a = acc + 10 * (size_t)id;
+                real* a = acc + 10 * (size_t)id;
                 for (int c = 0; c < 3; ++c) a[6 + c] += alpha * T * dch[c];
                 a[9] += alpha * T * dch[3];
                 /* alpha = min(0.99, op G): gradient passes through the clamp (upstream) */
-                const double Gv = Gs[k];
-                const double dL_dG = q->op * dL_dalpha_k;
+                const real Gv = Gs[k];
+                const real dL_dG = q->op * dL_dalpha_k;
                 a[5] += Gv * dL_dalpha_k;
-                const double dx = q->x - (double)px, dy = q->y - (double)py;
+                const real dx = q->x - pxf, dy = q->y - pyf;
                 /* power = -0.5 (A dx^2 + C dy^2) - B dx dy */
                 a[0] += dL_dG * Gv * (-q->ca * dx - q->cb * dy);
                 a[1] += dL_dG * Gv * (-q->cc * dy - q->cb * dx);
                 a[2] += dL_dG * Gv * (-0.5 * dx * dx);
                 a[3] += dL_dG * Gv * (-dx * dy);
                 a[4] += dL_dG * Gv * (-0.5 * dy * dy);
+                if (acc_abs) {
+                    real* b = acc_abs + 10 * (size_t)id;
+                    const real aG = fabs(q->op) * abs_dalpha_k * Gv;
+                    for (int c = 0; c < 3; ++c) b[6 + c] += fabs(alpha * T * dch[c]);
+                    b[9] += fabs(alpha * T * dch[3]);
+                    b[5] += Gv * abs_dalpha_k;
+                    b[0] += aG * (fabs(q->ca * dx) + fabs(q->cb * dy));
+                    b[1] += aG * (fabs(q->cc * dy) + fabs(q->cb * dx));
+                    b[2] += aG * (0.5 * dx * dx);
+                    b[3] += aG * fabs(dx * dy);
+                    b[4] += aG * (0.5 * dy * dy);
+                }
             }
         }
-    /* per-Gaussian chain rule */
+    free(used); free(Gs); free(alphas); free(list); free(g);
+    return 0;
+}
+
+/* Stage 2, the per-Gaussian chain rule: the gradients gvfo64_backward() returns, from the accumulators it is given.  Linear in acc_in.
+ * Outputs may be NULL.  g_means2D[P][2]: NDC convention (see header).  out_flag[P] (may be NULL): FLAG_* bits. */
+int SYM(chain)(SCENE_PARAMS, const real* acc_in, real* g_means3D, real* g_means2D, real* g_shs, real* g_colors, real* g_opac,
+               real* g_scales, real* g_rots, real* g_cov3D, uint8_t* out_flag) {
+    Scene s;
+    make_scene(&s, SCENE_ARGS);
     for (int i = 0; i < P; ++i) {
-        const G64* q = &g[i];
-        const double* a = acc + 10 * (size_t)i;
-        double gm[3] = {0, 0, 0}, gsc[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0}, gc6[6] = {0, 0, 0, 0, 0, 0}, gop = 0, gcol[3] = {0, 0, 0};
-        double gm2[2] = {0, 0};
+        G64 gi;
+        pre_one(&s, i, &gi);
+        const G64* q = &gi;
+        if (out_flag) out_flag[i] = (uint8_t)gi.flag;
+        const real* a = acc_in + 10 * (size_t)i;
+        real gm[3] = {0, 0, 0}, gsc[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0}, gc6[6] = {0, 0, 0, 0, 0, 0}, gop = 0, gcol[3] = {0, 0, 0};
+        real gm2[2] = {0, 0};
         if (q->visible) {
-            const double* p = means3D + 3 * (size_t)i;
+            const real* p = means3D + 3 * (size_t)i;
             /* screen-space mean: px = ((ndc + 1) W - 1) / 2 */
-            gm2[0] = a[0] * 0.5 * (double)W; gm2[1] = a[1] * 0.5 * (double)H;
+            gm2[0] = a[0] * 0.5 * (real)W; gm2[1] = a[1] * 0.5 * (real)H;
             {
-                const double* m = proj;
-                double mw = q->pw;
-                double mul1 = q->ph[0] * mw * mw, mul2 = q->ph[1] * mw * mw;
+                const real* m = proj;
+                real mw = q->pw;
+                real mul1 = q->ph[0] * mw * mw, mul2 = q->ph[1] * mw * mw;
                 gm[0] += (m[0] * mw - m[3] * mul1) * gm2[0] + (m[1] * mw - m[3] * mul2) * gm2[1];
                 gm[1] += (m[4] * mw - m[7] * mul1) * gm2[0] + (m[5] * mw - m[7] * mul2) * gm2[1];
                 gm[2] += (m[8] * mw - m[11] * mul1) * gm2[0] + (m[9] * mw - m[11] * mul2) * gm2[1];
             }
             /* depth output: depth = view row 2 . p */
-            gm[0] += view[2] * a[9]; gm[1] += view[6] * a[9]; gm[2] += view[10] * a[9];
+            gm[0] += view[2] * a[9]; if (!MUT(5)) gm[1] += view[6] * a[9]; gm[2] += view[10] * a[9];
             /* colour */
             if (colors_precomp) {
                 for (int c = 0; c < 3; ++c) gcol[c] = a[6 + c];
             } else {
-                double b[16], db[16][3];
+                real b[16], db[16][3];
                 sh_basis(deg, q->dir[0], q->dir[1], q->dir[2], b);
                 sh_basis_grad(deg, q->dir[0], q->dir[1], q->dir[2], db);
                 int nb = (deg + 1) * (deg + 1);
-                const double* sh = shs + (size_t)i * M * 3;
-                double ddir[3] = {0, 0, 0};
+                const real* sh = shs + (size_t)i * M * 3;
+                real ddir[3] = {0, 0, 0};
                 for (int c = 0; c < 3; ++c) {
-                    double gr = q->clamped[c] ? 0.0 : a[6 + c];
+                    real gr = q->clamped[c] ? 0.0 : a[6 + c];
                     for (int kk = 0; kk < nb; ++kk) {
                         if (g_shs) g_shs[((size_t)i * M + kk) * 3 + c] = b[kk] * gr;
                         for (int e = 0; e < 3; ++e) ddir[e] += db[kk][e] * sh[kk * 3 + c] * gr;
                     }
                 }
                 /* dir = d / |d| */
-                double dot = ddir[0] * q->dir[0] + ddir[1] * q->dir[1] + ddir[2] * q->dir[2];
-                for (int e = 0; e < 3; ++e) gm[e] += (ddir[e] - q->dir[e] * dot) / q->dlen;
+                real dot = ddir[0] * q->dir[0] + ddir[1] * q->dir[1] + ddir[2] * q->dir[2];
+                if (!MUT(1)) for (int e = 0; e < 3; ++e) gm[e] += (ddir[e] - q->dir[e] * dot) / q->dlen;
             }
             /* opacity and the mip coefficient */
             gop = a[5] * q->coef;
-            double gcxx = 0, gcxy = 0, gcyy = 0;   /* d/d(cov2D before the filter) */
-            const double k = mode == MODE_MIP ? kernel_size : 0.3;
+            real gcxx = 0, gcxy = 0, gcyy = 0;   /* d/d(cov2D before the filter) */
+            const real k = mode == MODE_MIP ? kernel_size : 0.3;
             if (mode == MODE_MIP && q->coef > 0.0) {
-                double dcoef = a[5] * opac[i];
-                double det0 = q->cxx * q->cyy - q->cxy * q->cxy, det1 = (q->cxx + k) * (q->cyy + k) - q->cxy * q->cxy;
+                real dcoef = a[5] * opac[i];
+                real det0 = q->cxx * q->cyy - q->cxy * q->cxy, det1 = (q->cxx + k) * (q->cyy + k) - q->cxy * q->cxy;
                 /* coef = sqrt(r + 1e-6), r = det0 / (det1 + 1e-6); neither det is clamped here (coef > 0) */
-                double dr = dcoef * 0.5 / q->coef;
-                double dd0 = dr / (det1 + 1e-6), dd1 = -dr * det0 / ((det1 + 1e-6) * (det1 + 1e-6));
+                real dr = dcoef * 0.5 / q->coef;
+                real dd0 = dr / (det1 + 1e-6), dd1 = -dr * det0 / ((det1 + 1e-6) * (det1 + 1e-6));
+                if (MUT(6)) dd1 = 0;
                 gcxx += dd0 * q->cyy + dd1 * (q->cyy + k);
                 gcyy += dd0 * q->cxx + dd1 * (q->cxx + k);
                 gcxy += -2.0 * q->cxy * (dd0 + dd1);
             }
             /* conic = inverse of the filtered cov2D (a', b', c') */
             {
-                double ap = q->cxx + k, bp = q->cxy, cp = q->cyy + k;
-                double det = ap * cp - bp * bp, d2 = 1.0 / (det * det);
-                double gA = a[2], gB = a[3], gC = a[4];
+                real ap = q->cxx + k, bp = q->cxy, cp = q->cyy + k;
+                real det = ap * cp - bp * bp, d2 = 1.0 / (det * det);
+                real gA = a[2], gB = a[3], gC = a[4];
                 gcxx += d2 * (-cp * cp * gA + bp * cp * gB - bp * bp * gC);
                 gcxy += d2 * (2 * bp * cp * gA - (det + 2 * bp * bp) * gB + 2 * ap * bp * gC);
                 gcyy += d2 * (-bp * bp * gA + ap * bp * gB - ap * ap * gC);
             }
             /* cov2D = [A0; A1] Sigma [A0; A1]^T */
-            const double* c6 = q->c6;
-            double S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-            double Gm[3][3];
+            const real* c6 = q->c6;
+            real S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
+            real Gm[3][3];
             for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c)
                 Gm[r][c] = gcxx * q->A0[r] * q->A0[c] + gcxy * q->A0[r] * q->A1[c] + gcyy * q->A1[r] * q->A1[c];
             gc6[0] = Gm[0][0]; gc6[3] = Gm[1][1]; gc6[5] = Gm[2][2];
             gc6[1] = Gm[0][1] + Gm[1][0]; gc6[2] = Gm[0][2] + Gm[2][0]; gc6[4] = Gm[1][2] + Gm[2][1];
-            double dA0[3], dA1[3];
+            real dA0[3], dA1[3];
             for (int r = 0; r < 3; ++r) {
-                double SA0 = S[r][0] * q->A0[0] + S[r][1] * q->A0[1] + S[r][2] * q->A0[2];
-                double SA1 = S[r][0] * q->A1[0] + S[r][1] * q->A1[1] + S[r][2] * q->A1[2];
+                real SA0 = S[r][0] * q->A0[0] + S[r][1] * q->A0[1] + S[r][2] * q->A0[2];
+                real SA1 = S[r][0] * q->A1[0] + S[r][1] * q->A1[1] + S[r][2] * q->A1[2];
                 dA0[r] = 2 * gcxx * SA0 + gcxy * SA1;
                 dA1[r] = 2 * gcyy * SA1 + gcxy * SA0;
             }
-            double dJ00 = 0, dJ02 = 0, dJ11 = 0, dJ12 = 0;
+            real dJ00 = 0, dJ02 = 0, dJ11 = 0, dJ12 = 0;
             for (int c = 0; c < 3; ++c) {
-                double w0 = view[c * 4 + 0], w1 = view[c * 4 + 1], w2 = view[c * 4 + 2];
+                real w0 = view[c * 4 + 0], w1 = view[c * 4 + 1], w2 = view[c * 4 + 2];
                 dJ00 += dA0[c] * w0; dJ02 += dA0[c] * w2; dJ11 += dA1[c] * w1; dJ12 += dA1[c] * w2;
             }
-            double fx = (double)W / (2.0 * tanfovx), fy = (double)H / (2.0 * tanfovy);
-            double tz = q->tz, tz2 = 1.0 / (tz * tz), tz3 = tz2 / tz;
-            double dtx = q->xmul * (-fx * tz2 * dJ02), dty = q->ymul * (-fy * tz2 * dJ12);
-            double dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + 2 * fx * q->tx * tz3 * dJ02 + 2 * fy * q->ty * tz3 * dJ12;
+            real fx = (real)W / (2.0 * tanfovx), fy = (real)H / (2.0 * tanfovy);
+            real tz = q->tz, tz2 = 1.0 / (tz * tz), tz3 = tz2 / tz;
+            real dtx = (MUT(4) ? (real)1 : q->xmul) * (-fx * tz2 * dJ02), dty = (MUT(4) ? (real)1 : q->ymul) * (-fy * tz2 * dJ12);
+            real dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + 2 * fx * q->tx * tz3 * dJ02 + 2 * fy * q->ty * tz3 * dJ12;
+            if (MUT(3)) dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11;
             /* t = W p + ... */
             gm[0] += view[0] * dtx + view[1] * dty + view[2] * dtz;
             gm[1] += view[4] * dtx + view[5] * dty + view[6] * dtz;
             gm[2] += view[8] * dtx + view[9] * dty + view[10] * dtz;
             /* Sigma = L L^T, L = R diag(mod s) */
             if (!cov3D) {
-                const double* sv = scales + 3 * (size_t)i;
-                const double* qq = rots + 4 * (size_t)i;
-                double r = qq[0], x = qq[1], y = qq[2], z = qq[3];
-                double R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
+                const real* sv = scales + 3 * (size_t)i;
+                const real* qq = rots + 4 * (size_t)i;
+                real r = qq[0], x = qq[1], y = qq[2], z = qq[3];
+                real R[3][3] = {{1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y)},
                                   {2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x)},
                                   {2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)}};
-                double sc[3] = {scale_mod * sv[0], scale_mod * sv[1], scale_mod * sv[2]};
-                double Gs2[3][3] = {{gc6[0], 0.5 * gc6[1], 0.5 * gc6[2]}, {0.5 * gc6[1], gc6[3], 0.5 * gc6[4]}, {0.5 * gc6[2], 0.5 * gc6[4], gc6[5]}};
-                double dLm[3][3], dR[3][3];
+                real sc[3] = {scale_mod * sv[0], scale_mod * sv[1], scale_mod * sv[2]};
+                real Gs2[3][3] = {{gc6[0], 0.5 * gc6[1], 0.5 * gc6[2]}, {0.5 * gc6[1], gc6[3], 0.5 * gc6[4]}, {0.5 * gc6[2], 0.5 * gc6[4], gc6[5]}};
+                real dLm[3][3], dR[3][3];
                 for (int r2 = 0; r2 < 3; ++r2) for (int c = 0; c < 3; ++c) {
-                    double v = 0;
+                    real v = 0;
                     for (int kk = 0; kk < 3; ++kk) v += 2 * Gs2[r2][kk] * R[kk][c] * sc[c];
                     dLm[r2][c] = v;
                 }
                 for (int c = 0; c < 3; ++c) {
-                    double v = 0;
+                    real v = 0;
                     for (int r2 = 0; r2 < 3; ++r2) { v += dLm[r2][c] * R[r2][c]; dR[r2][c] = dLm[r2][c] * sc[c]; }
                     gsc[c] = scale_mod * v;
                 }
-                gq[0] = 2 * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
+                gq[0] = 2 * ((MUT(7) ? z : -z) * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
                 gq[1] = 2 * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2 * x * dR[1][1] - r * dR[1][2] + z * dR[2][0] + r * dR[2][1] - 2 * x * dR[2][2]);
                 gq[2] = 2 * (-2 * y * dR[0][0] + x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] + z * dR[2][1] - 2 * y * dR[2][2]);
                 gq[3] = 2 * (-2 * z * dR[0][0] - r * dR[0][1] + x * dR[0][2] + r * dR[1][0] - 2 * z * dR[1][1] + y * dR[1][2] + x * dR[2][0] + y * dR[2][1]);
@@ -475,6 +586,16 @@ int gvfo64_backward(int P, int M, int deg, const double* means3D, const double* 
             for (int kk = nb; kk < M; ++kk) for (int c = 0; c < 3; ++c) g_shs[((size_t)i * M + kk) * 3 + c] = 0.0;
         }
     }
-    free(used); free(Gs); free(alphas); free(acc); free(list); free(g);
+    return 0;
+}
+
+/* Gradients of  L = sum(dL_dcolor * color) + sum(dL_dalpha * alpha) + sum(dL_ddepth * depth)  w.r.t. every input: the composition of the
+ * two stages.  Outputs may be NULL.  g_means2D[P][2]: NDC convention (see header). */
+int SYM(backward)(SCENE_PARAMS, const real* dL_dcolor, const real* dL_dalpha, const real* dL_ddepth, real* g_means3D, real* g_means2D,
+                  real* g_shs, real* g_colors, real* g_opac, real* g_scales, real* g_rots, real* g_cov3D) {
+    real* acc = (real*)malloc(sizeof(real) * 10 * (size_t)(P > 0 ? P : 1));
+    SYM(accumulators)(SCENE_ARGS, NULL, dL_dcolor, dL_dalpha, dL_ddepth, acc, NULL, NULL, NULL);
+    SYM(chain)(SCENE_ARGS, acc, g_means3D, g_means2D, g_shs, g_colors, g_opac, g_scales, g_rots, g_cov3D, NULL);
+    free(acc);
     return 0;
 }

@@ -126,7 +126,7 @@ def test_matches_the_double_oracle(cuda):
         torch.autograd.backward(act, gouts)
     gref = {k: getattr(gmc, k).grad for k in RAW}
     gref["delta"] = dc.grad
-    _compare(gb, gref, 2e-3, "batched vs double oracle:")
+    _compare(gb, gref, 6e-6, "batched vs double oracle:")     # measured 1.6e-06 .. 3.0e-06 (_xyz, delta): twice the worst
 
 
 def test_every_record_layout_gives_the_same_gradients(cuda, monkeypatch):

@@ -1,5 +1,8 @@
 """Backward pass of the HIP rasteriser operator (gvf_rast_backward through torch.autograd) against the double-precision
-oracle (oracle/rast_bwd_oracle.c, itself pinned by finite differences in tests/test_oracle_rast_bwd.py) -- needs an MI355X."""
+oracle (oracle/rast_bwd_oracle.c, itself pinned by finite differences in tests/test_oracle_rast_bwd.py) -- needs an MI355X.
+
+These are end-to-end checks through autograd with one whole-tensor relative L2 per gradient; the per-Gaussian, stage-wise conformance of
+the same kernels (blend backward and chain rule separately, against the fp32 yardstick) is tests/test_rast_bwd_conformance_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -51,8 +54,10 @@ def test_gradients_match_double_oracle(cuda, mode, deg, H, W, P):
     errs["means2D"] = rel(n(m2.grad)[:, :2], ref["means2D"])
     print(f"mode={mode} deg={deg} {H}x{W} P={P}: " + " ".join(f"{k}={v:.1e}" for k, v in errs.items()))
     assert float(m2.grad[:, 2].abs().max()) == 0.0
+    # measured 1.6e-06 .. 8.5e-06 over the four cases and six tensors (worst: scales at P = 8000); the bar is twice the worst.  A whole-tensor
+    # norm cannot see one wrong term of the chain rule (test_rast_bwd_conformance_gpu.py does, per Gaussian); it guards the end-to-end path.
     for k, v in errs.items():
-        assert v < 2e-3, (k, v)
+        assert v < 2e-5, (k, v)
 
 
 def test_precomputed_colour_and_covariance_gradients(cuda):
@@ -81,7 +86,7 @@ def test_precomputed_colour_and_covariance_gradients(cuda):
     for name, got in (("means3D", m3.grad), ("colors_precomp", col.grad), ("opacities", op.grad), ("cov3D_precomp", cov.grad)):
         e = rel(n(got).reshape(ref[name].shape), ref[name])
         print(name, f"{e:.1e}")
-        assert e < 2e-3, (name, e)
+        assert e < 1e-5, (name, e)                                    # measured 2.5e-06 .. 5.0e-06 (means3D): twice the worst
 
 
 def test_no_grad_path_is_unchanged_and_backward_needs_its_own_workspace(cuda):
