@@ -27,6 +27,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-
 SOURCES = {
     "sort.hip": [],
     "rast.hip": ["-ffp-contract=off"],
+    "rast_front.hip": ["-ffp-contract=off"],
     "rast_sort.hip": ["-ffp-contract=off"],
     "rast_blend.hip": ["-ffp-contract=off"],
     "rast_bwd.hip": ["-ffp-contract=off"],

@@ -39,6 +39,14 @@ class GvfGaussianActivation(ctypes.Structure):
                 ("min_kernel_size", ctypes.c_float), ("scaling_activation", ctypes.c_int32)]
 
 
+class GvfRastPlan(ctypes.Structure):
+    """What a forward call decides before its first launch (gvf_rast_call_plan; include/gvf_rast.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("bucket", "shared", "index_count", "morton", "slot_mode", "rec_gather", "wave_frames",
+                                              "order_tiles", "upstream_binning", "n_slices", "layout", "gx", "gy", "ntiles", "nb", "nseg")] + \
+               [(n, ctypes.c_int32 * 2) for n in ("pre_grid", "wf_grid", "bin_grid", "binx_grid")] + \
+               [(n, ctypes.c_int32) for n in ("scan_blocks", "clear_blocks", "pre_lds_bytes", "wf_lds_bytes")]
+
+
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
 # name -> (restype, argtypes); mirrors include/*.h one to one (checked by tests/test_capi_symbols.py)
@@ -65,6 +73,9 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "gvf_rgb_to_u8": (_i, [_vp, _vp, _i64, _vp]),
     "gvf_rast_sort_class_counts": (_i, [_vp, _sz, _i, _i, _i, _i, _i64, ctypes.POINTER(ctypes.c_uint32), _vp]),
+    "gvf_rast_call_plan": (_i, [ctypes.POINTER(GvfRastSettings), ctypes.POINTER(GvfRastFrame), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64,
+                                ctypes.POINTER(GvfRastPlan)]),
+    "gvf_rast_slice_groups": (_i, [ctypes.POINTER(GvfRastFrame), _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i)]),
     "gvf_rast_profile_enable": (_i, [_i]),
     "gvf_rast_profile_read": (_i, [ctypes.POINTER(_f), ctypes.POINTER(_i)]),
     "gvf_rast_shared_activation_calls": (_i64, []),

@@ -630,6 +630,16 @@ __global__ __launch_bounds__(PRE_THREADS) void activation_backward_kernel(
     }
 }
 
+// blend_backward over (tiles, F frames) of the forward call's workspace; AUX when the alpha / depth outputs carry gradients
+void launch_blend_backward(hipStream_t stream, const GvfRastSettings& st, int P, int F, const Workspace& w, const float* subpixel_offset,
+                           const float* dL_dcolor, const float* dL_dalpha, const float* dL_ddepth, float* acc) {
+    const int H = st.image_height, W = st.image_width;
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    auto* kernel = (dL_dalpha != nullptr || dL_ddepth != nullptr) ? blend_backward_kernel<true> : blend_backward_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(gx * gy, F), dim3(BLEND_THREADS), 0, stream, P, H, W, gx, st.bg[0], st.bg[1], st.bg[2], w.ranges, w.ids,
+                       w.splats, subpixel_offset, dL_dcolor, dL_dalpha, dL_ddepth, acc, w.mm + LAYOUT_WORD, w.order_alt);
+}
+
 }  // namespace
 
 extern "C" int gvf_rast_backward_scratch_bytes(int P, size_t* bytes) {
@@ -669,19 +679,9 @@ extern "C" int gvf_rast_backward(const GvfRastSettings* st, const GvfRastFrame* 
     // the layout of the forward call's workspace: same (P, F = 1, H, W, max_rendered) => same carve
     Workspace w = carve(const_cast<void*>(workspace), workspace_bytes, P, 1, H, W, max_rendered);
     if (!w.ok) return GVF_ENOSPC;
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, ntiles = gx * gy;
     float* acc = (float*)scratch;
     if (hipMemsetAsync(acc, 0, (size_t)P * BWD_ACC * sizeof(float), stream) != hipSuccess) return GVF_ELAUNCH;
-    if (max_rendered > 0) {
-        if (dL_dalpha != nullptr || dL_ddepth != nullptr)
-            hipLaunchKernelGGL(blend_backward_kernel<true>, dim3(ntiles), dim3(BLEND_THREADS), 0, stream, P, H, W, gx, st->bg[0],
-                               st->bg[1], st->bg[2], w.ranges, w.ids, w.splats, subpixel_offset, dL_dcolor, dL_dalpha, dL_ddepth, acc,
-                               w.mm + LAYOUT_WORD, w.order_alt);
-        else
-            hipLaunchKernelGGL(blend_backward_kernel<false>, dim3(ntiles), dim3(BLEND_THREADS), 0, stream, P, H, W, gx, st->bg[0],
-                               st->bg[1], st->bg[2], w.ranges, w.ids, w.splats, subpixel_offset, dL_dcolor, dL_dalpha, dL_ddepth, acc,
-                               w.mm + LAYOUT_WORD, w.order_alt);
-    }
+    if (max_rendered > 0) launch_blend_backward(stream, *st, P, 1, w, subpixel_offset, dL_dcolor, dL_dalpha, dL_ddepth, acc);
     GVF_CHECK_LAUNCH();
     BwdParams bp;
     bp.P = P; bp.M = M; bp.deg = st->sh_degree; bp.H = H; bp.W = W; bp.mode = st->mode;
@@ -738,30 +738,15 @@ extern "C" int gvf_rast_backward_batched(const GvfRastSettings* st, const GvfRas
     Workspace w = carve(const_cast<void*>(workspace), workspace_bytes, P, F, H, W, max_rendered);   // the forward call's carve
     if (!w.ok) return GVF_ENOSPC;
     if (P == 0) return GVF_OK;
-    // frames grouped by delta slice (slices in order of first use): [F] frames | [ns + 1] starts | [ns] delta indices
-    std::vector<int32_t> di_of((size_t)F), slices;
-    for (int f = 0; f < F; ++f) {
-        di_of[(size_t)f] = (delta != nullptr && frames_host[f].delta_index >= 0) ? frames_host[f].delta_index : -1;
-        bool seen = false;
-        for (int32_t d : slices) seen = seen || d == di_of[(size_t)f];
-        if (!seen) slices.push_back(di_of[(size_t)f]);
-    }
+    // frames grouped by delta slice (slices in order of first use, as the forward's plan groups them; no limit on their number here):
+    // [F] frames | [ns + 1] starts | [ns] delta indices
+    std::vector<int32_t> slices, frame_slice;
+    group_slices(frames_host, F, delta != nullptr, 0, slices, frame_slice);
     const int ns = (int)slices.size();
-    std::vector<int32_t> tab;
-    tab.reserve(3 * (size_t)F + 1);
-    std::vector<int32_t> starts;
-    for (int k = 0; k < ns; ++k) {
-        starts.push_back((int32_t)tab.size());
-        for (int f = 0; f < F; ++f)
-            if (di_of[(size_t)f] == slices[(size_t)k]) tab.push_back(f);
-    }
-    starts.push_back((int32_t)tab.size());
-    tab.insert(tab.end(), starts.begin(), starts.end());
-    tab.insert(tab.end(), slices.begin(), slices.end());
+    const std::vector<int32_t> tab = slice_table(slices, frame_slice);
 
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, ntiles = gx * gy;
     float* acc = (float*)scratch;
     const size_t acc_bytes = (size_t)F * P * BWD_ACC * sizeof(float);
     int32_t* groups = reinterpret_cast<int32_t*>((char*)scratch + gvf_align_up(acc_bytes, 256));
@@ -774,16 +759,7 @@ extern "C" int gvf_rast_backward_batched(const GvfRastSettings* st, const GvfRas
         for (int k = 0; k < cnt; ++k) c.v[k] = tab[k0 + (size_t)k];
         hipLaunchKernelGGL(upload_ints_kernel, dim3(1), dim3(256), 0, stream, c, cnt, groups + k0);
     }
-    if (max_rendered > 0) {
-        if (dL_dalpha != nullptr || dL_ddepth != nullptr)
-            hipLaunchKernelGGL(blend_backward_kernel<true>, dim3(ntiles, F), dim3(BLEND_THREADS), 0, stream, P, H, W, gx, st->bg[0],
-                               st->bg[1], st->bg[2], w.ranges, w.ids, w.splats, nullptr, dL_dcolor, dL_dalpha, dL_ddepth, acc,
-                               w.mm + LAYOUT_WORD, w.order_alt);
-        else
-            hipLaunchKernelGGL(blend_backward_kernel<false>, dim3(ntiles, F), dim3(BLEND_THREADS), 0, stream, P, H, W, gx, st->bg[0],
-                               st->bg[1], st->bg[2], w.ranges, w.ids, w.splats, nullptr, dL_dcolor, dL_dalpha, dL_ddepth, acc,
-                               w.mm + LAYOUT_WORD, w.order_alt);
-    }
+    if (max_rendered > 0) launch_blend_backward(stream, *st, P, F, w, nullptr, dL_dcolor, dL_dalpha, dL_ddepth, acc);
     GVF_CHECK_LAUNCH();
     BwdBatchedParams bp;
     bp.P = P; bp.M = M; bp.H = H; bp.W = W; bp.mode = st->mode; bp.F = F; bp.nslices = ns;

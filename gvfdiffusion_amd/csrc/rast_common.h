@@ -1,14 +1,16 @@
-// rast_common.h -- internal to the rasteriser's translation units (rast.hip = front end + host pipeline, rast_sort.hip = per-tile sort,
-// rast_blend.hip = blend, rast_bwd.hip = backward): the constants and device helpers more than one stage uses, and the host functions through
-// which the stages meet.  Every kernel is defined and launched in ONE of those files; nothing here holds process state.
+// rast_common.h -- internal to the rasteriser's translation units (rast.hip = host pipeline + entry points, rast_front.hip = front end,
+// rast_sort.hip = per-tile sort, rast_blend.hip = blend, rast_bwd.hip = backward): the constants and device helpers more than one stage uses,
+// and the host functions through which the stages meet (the call plan they take: rast_plan.h).  Every kernel is defined and launched in ONE
+// of those files; nothing here holds process state.
 #pragma once
 #include "gvf_common.h"
 #include "../../include/gvf_rast.h"
+#include "rast_plan.h"
+using namespace gvf_rast;
+static_assert(WAVE == GVF_WAVE, "rast_plan.h sizes its grids for this wave width");
 
 namespace {
 
-constexpr int PRE_THREADS = 256;
-constexpr int TILE = GVF_TILE;
 constexpr int BLEND_THREADS = TILE * TILE;
 constexpr int MAX_SH_COEFFS = 16;
 // The splat record holds the conic PRE-SCALED for the blend: (a, b, c) -> (CONIC_K1 a, CONIC_K2 b, CONIC_K1 c), so that
@@ -263,12 +265,12 @@ __device__ __forceinline__ TileRect get_rect(float px, float py, float radius, i
     return r;
 }
 
-// Size classes of the per-tile sort (R4, rast_sort.hip; seg_scan_kernel in rast.hip files the segments by them).  SORT_SMALL_N: segments of up to this many keys are sorted in static LDS by tile_sort_kernel<0>, one
+// Size classes of the per-tile sort (R4, rast_sort.hip; seg_scan_kernel in rast_front.hip files the segments by them).  SORT_SMALL_N: segments of up to this many keys are sorted in static LDS by tile_sort_kernel<0>, one
 // workgroup of 256 threads each.  1536 since the end of round 6 (2048 before): 12 bytes of LDS per key = 18.4 KiB = EIGHT workgroups per CU instead
 // of six -- the launch lives on how many segments are in flight (its waves are parked 75 % of the time) --; the few segments of 1537-2048 keys join
 // the 512-thread LDS class.  Tile sort 0.137 -> 0.119 ms at the bench shape, the live render job -4 % (profiles/r06_tile_sort_classes.txt; sorting
 // the segments of up to 256-512 keys four to a workgroup, one WAVE each, was built and measured on top of it: -3 % of the launch at best, not kept).
-#ifndef GVF_SORT_SMALL_N                // (a variant build passes it to rast.hip AND rast_sort.hip)
+#ifndef GVF_SORT_SMALL_N                // (a variant build passes it to rast_front.hip AND rast_sort.hip)
 #define GVF_SORT_SMALL_N 1536
 #endif
 constexpr int SORT_SMALL_N = GVF_SORT_SMALL_N;
@@ -319,12 +321,6 @@ __device__ __forceinline__ unsigned quadrant_mask(float x, float y, float ap, fl
     return m;
 }
 
-// The record layout a forward call chose, kept in a workspace word (mm[LAYOUT_WORD], beside the bounding box) for the backward of that
-// call, which reads it on the device: run_pipeline's decision is not made a second time, and no host read is needed (capture-safe).
-//   bit 0 (LAYOUT_SLOT_ORDER): splat records of a frame sit at the Gaussians' Morton slots, rec = order_alt[id] (blend_rec_of); else rec = id
-constexpr int LAYOUT_WORD = 6;
-constexpr uint32_t LAYOUT_SLOT_ORDER = 1u;
-
 constexpr int BWD_ACC = 10;   // per Gaussian: d/dx, d/dy [pixels], d/d(conic a, b, c), d/d(opacity_eff), d/d(r, g, b), d/d(depth)
 
 }  // namespace
@@ -348,6 +344,31 @@ struct Workspace {
 
 // rast.hip: the layout of a call's workspace -- the forward and the backward of a call carve it with the same arguments
 Workspace carve(void* ws, size_t bytes, int P, int F, int H, int W, int64_t max_rendered);
+
+// One forward call's arguments, as the entry points hand them to the pipeline and the pipeline to the front end.  Inputs are either
+// activated tensors (fused = false: a0 = means3D, a1 = scales, a2 = rotations, a3 = opacities, sh = shs) or raw GaussianModel parameters
+// (fused: a0 = _xyz, a1 = _scaling, a2 = _rotation, a3 = _opacity, sh = _features_dc, delta[n_delta][P][14]).
+struct RastCall {
+    const GvfRastSettings* st; const GvfRastFrame* frames_host; int F, P, M;
+    bool fused; const GvfGaussianActivation* act;
+    const float *a0, *a1, *a2, *a3, *sh, *colors_precomp, *cov3D_precomp, *delta; int n_delta;
+    const float* subpixel_offset;
+    int64_t max_rendered;
+    int32_t* out_radii; uint32_t* out_num_rendered;
+};
+
+// Stage-timer mark k of a profiled call (gvf_rast_profile_*): marks = the call's events, null when the call is not timed
+inline void prof_mark(hipStream_t s, const hipEvent_t* marks, int k) {
+    if (marks != nullptr) (void)hipEventRecord(marks[k], s);
+}
+
+// rast_front.hip: the launches in front of the per-tile sort, from the call's plan (rast_plan.h).  upload_frames: the camera blocks to
+// w.frames, and the call's tables cleared.  front_end_*: one per binning algorithm, marks 0 .. 5 at the stage boundaries; they leave the
+// tile ranges, the per-frame counts and the unsorted tile segments (bucket: keys in w.keys; radix: where *keys_sorted / *vals_by_tile say).
+int upload_frames(hipStream_t stream, const RastCall& c, const RastPlan& plan, const Workspace& w);
+int front_end_bucket(hipStream_t stream, const RastCall& c, const RastPlan& plan, const Workspace& w, const hipEvent_t* marks);
+int front_end_radix(hipStream_t stream, const RastCall& c, const RastPlan& plan, const Workspace& w, const hipEvent_t* marks,
+                    uint64_t** keys_sorted, uint32_t** vals_by_tile);
 
 // rast_sort.hip: classify + the size classes of the per-tile sort over nseg segments (cls: 2 + 2 nseg words of scratch; cls_state: see there)
 int launch_tile_sort(hipStream_t stream, const uint2* ranges, uint64_t* keys, const uint32_t* vals, uint32_t* ids, uint32_t* cls,

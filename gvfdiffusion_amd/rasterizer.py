@@ -425,8 +425,22 @@ def sort_class_counts(device=None):
     return int(out[0]), int(out[1])
 
 
+def call_plan(settings, frames, P, M, max_rendered, fused=True, has_sh=True, has_colors_precomp=False, has_cov3D_precomp=False,
+              has_delta=True, has_subpixel_offset=False):
+    """What a forward call with these arguments decides before its first launch (gvf_rast_call_plan: the path flags, the slice count,
+    the grids and LDS sizes of the path-dependent launches), as a _lib.GvfRastPlan.  Host only: no launch, no device memory; the
+    GVF_RAST_* environment switches are read as the forward reads them.  The defaults describe a rasterize_batched() call with deltas."""
+    F = len(frames)
+    arr = frames if isinstance(frames, ctypes.Array) else (_lib.GvfRastFrame * F)(*frames)
+    out = _lib.GvfRastPlan()
+    _lib.check(_lib.lib().gvf_rast_call_plan(ctypes.byref(settings), arr, F, int(P), int(M), int(fused), int(has_sh), int(has_colors_precomp),
+                                             int(has_cov3D_precomp), int(has_delta), int(has_subpixel_offset), int(max_rendered),
+                                             ctypes.byref(out)), "gvf_rast_call_plan")
+    return out
+
+
 def gaussian_activate(act, xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta=None):
-    """GaussianModel.get_*_with_delta on the device (csrc/rast.hip activate_kernel)."""
+    """GaussianModel.get_*_with_delta on the device (csrc/rast_front.hip activate_kernel)."""
     _lib.require_cuda(xyz_raw)
     dev = xyz_raw.device
     xyz_raw, features_dc = _f32c(xyz_raw, "xyz"), _f32c(features_dc, "features_dc")

@@ -254,6 +254,37 @@ int64_t gvf_rast_shared_activation_calls(void);
 int gvf_rast_sort_class_counts(const void* workspace, size_t workspace_bytes, int P, int F, int H, int W, int64_t max_rendered,
                                uint32_t* counts_host /*[2]*/, void* stream);
 
+/* Diagnostic of the host pipeline: what a gvf_rast_forward*() call with these arguments decides before its first launch -- which path
+ * it takes and the shapes of the launches that depend on the path.  Flags are 0 / 1.  Runs no launch and touches no device memory
+ * (frames_host is read for the delta indices only); reads the GVF_RAST_* environment switches exactly as the forward does, per call.
+ *   bucket: bucket binning (bin_algo != RADIX);  shared: shared activation (once per (delta slice, Gaussian));  index_count: the count pass
+ *   walks the bin records in index order;  morton: the Gaussians are put in Morton order;  slot_mode: records at the Morton slots (layout =
+ *   1);  rec_gather: the bin passes gather index-ordered records in Morton order;  wave_frames: the projection launch runs 64 Gaussians
+ *   per workgroup, one frame per wave at a time;  order_tiles: the blend takes the heaviest tiles first;  upstream_binning: whole
+ *   3-sigma tile rects are binned (asked for, or sub-pixel offsets given).
+ *   n_slices: distinct delta slices of the frames, in order of first use, counted up to 16 (a frame without a delta is one slice).
+ *   gx, gy, ntiles: the tile grid;  nb = ceil(P / 256);  nseg = F * ntiles.
+ *   pre_grid / pre_lds_bytes: the projection launch on its 256-Gaussian mapping;  wf_grid / wf_lds_bytes: on the wave-frames mapping;
+ *   bin_grid: the count / scatter passes in Morton order;  binx_grid: the index-ordered count pass;  scan_blocks: the segment scan's two
+ *   launches;  clear_blocks: the blocks of the upload launch that clear the call's tables. */
+typedef struct GvfRastPlan {
+    int32_t bucket, shared, index_count, morton, slot_mode, rec_gather, wave_frames, order_tiles, upstream_binning;
+    int32_t n_slices, layout;
+    int32_t gx, gy, ntiles, nb, nseg;
+    int32_t pre_grid[2], wf_grid[2], bin_grid[2], binx_grid[2];
+    int32_t scan_blocks, clear_blocks;
+    int32_t pre_lds_bytes, wf_lds_bytes;
+} GvfRastPlan;
+int gvf_rast_call_plan(const GvfRastSettings* settings_host, const GvfRastFrame* frames_host, int F, int P, int M, int fused,
+                       int has_sh, int has_colors_precomp, int has_cov3D_precomp, int has_delta, int has_subpixel_offset,
+                       int64_t max_rendered, GvfRastPlan* out);
+
+/* Diagnostic of the frames' grouping by delta slice, which the forward's plan and the batched backward share: writes the table the
+ * backward uploads -- [F] frame indices grouped by slice (slices in order of first use, frames ascending inside one) | [n + 1] group
+ * starts | [n] the slices' delta indices (-1: no delta) -- to table_host (room for 3 F + 1 words) and n to *n_slices.  max_slices > 0:
+ * GVF_ENOSPC when the frames select more distinct slices than that (the forward's limit is 16; the backward has none: 0). */
+int gvf_rast_slice_groups(const GvfRastFrame* frames_host, int F, int has_delta, int max_slices, int32_t* table_host, int* n_slices);
+
 /* Library identification: returns a static string "gvf_hip <version> gfx950". */
 const char* gvf_version(void);
 

@@ -1,7 +1,7 @@
 """Bucket binning of the fused launch on a Morton-hostile sample -- needs an MI355X.
 
 The fused launch (preprocess_kernel<false>) stores its bin records at the Gaussians' own indices and bins them in index order when a frame's
-tiles fit the whole-frame table (rast.hip, bin_index_kernel), over Morton slots otherwise; the shared-activation launch keeps its Morton-slot
+tiles fit the whole-frame table (rast_front.hip, bin_index_kernel), over Morton slots otherwise; the shared-activation launch keeps its Morton-slot
 layout.  A spatially presorted sample and a random permutation of it must give the same instance counts per frame, and on each of them the
 fused path must give the shared path's bits (same per-tile key sets -> same sorted lists -> same images)."""
 import os
@@ -39,6 +39,11 @@ def _render(cuda, attrs, delta, S, deg, shared):
         out = R.rasterize_batched(st, frames, gm.activation_struct(), *raw, delta=delta, want_alpha_depth=True, want_radii=True)
         torch.cuda.synchronize()
         n_shared = int(_lib.lib().gvf_rast_shared_activation_calls()) - before
+        # the call plan (host only, same switches): shared activation in slot order, or the fused wave-frames launch with records at the
+        # Gaussians' indices -- counted in index order when the frame's tiles fit the table (256 x 256), gathered in Morton order
+        plan = R.call_plan(st, frames, attrs["means3D"].shape[0], raw[1].shape[1], out["max_rendered"])
+        assert plan.shared == plan.slot_mode == int(shared) and plan.morton == 1
+        assert plan.wave_frames == plan.rec_gather == int(not shared) and plan.index_count == int(not shared and S == 256)
     finally:
         if old is None:
             os.environ.pop("GVF_RAST_SHARED_ACT", None)

@@ -267,7 +267,10 @@ def test_shared_activation_equals_fused_path(cuda, mode, deg, bin_algo):
         before = int(_lib.lib().gvf_rast_shared_activation_calls())
         out = R.rasterize_batched(st, frames, act, *raw, delta=delta, want_alpha_depth=True, want_radii=True)
         torch.cuda.synchronize()
-        return out, int(_lib.lib().gvf_rast_shared_activation_calls()) - before
+        took = int(_lib.lib().gvf_rast_shared_activation_calls()) - before
+        # the call plan (host only, same switches) says the same as the counter
+        assert bool(R.call_plan(st, frames, P, raw[1].shape[1], out["max_rendered"]).shared) == (took >= 1)
+        return out, took
 
     old_env = os.environ.get("GVF_RAST_SHARED_ACT")
     try:
@@ -307,8 +310,10 @@ def test_shared_activation_equals_fused_path(cuda, mode, deg, bin_algo):
     # four distinct slices for four frames: not worth a second launch, the call stays fused
     before = int(_lib.lib().gvf_rast_shared_activation_calls())
     four = [R.make_frame(c["viewmatrix"], c["projmatrix"], c["campos"], c["tanfovx"], c["tanfovy"], di) for c, di in zip(cams, [0, 1, 2, -1])]
-    R.rasterize_batched(st, four, act, *raw, delta=delta)
+    out4 = R.rasterize_batched(st, four, act, *raw, delta=delta)
     assert int(_lib.lib().gvf_rast_shared_activation_calls()) == before
+    plan4 = R.call_plan(st, four, P, raw[1].shape[1], out4["max_rendered"])
+    assert plan4.shared == 0 and plan4.n_slices == 4
 
 
 def test_blend_dispatch_order_heaviest_first_is_invisible(cuda):
@@ -438,9 +443,14 @@ def test_live_shape_frame_matches_oracle(cuda, oracle_lib, bin_algo):
     images = {}
     for upstream in ((False, True) if bin_algo == "bucket" else (False,)):         # (the radix run: one frame; oracle frames cached per session)
         st = R.make_settings(S, S, 0, _lib.RAST_MODE_MIP, rend.pipe.kernel_size, 1.0, (1.0, 1.0, 1.0), upstream_binning=upstream)
+        before = int(_lib.lib().gvf_rast_shared_activation_calls())
         out = R.rasterize_batched(st, frames, gm.activation_struct(), gm._xyz, gm.get_features, gm._scaling, gm._rotation, gm._opacity,
                                   delta=delta, want_radii=True)
         medium, huge = R.sort_class_counts(cuda)
+        # one frame: the per-frame fused path, by the counter and by the call plan
+        plan = R.call_plan(st, frames, P, gm.get_features.shape[1], out["max_rendered"])
+        assert int(_lib.lib().gvf_rast_shared_activation_calls()) == before and plan.shared == 0
+        assert plan.upstream_binning == int(upstream) and plan.bucket == int(bin_algo == "bucket")
         ref = cached(("live", 37, upstream), lambda: oracle_render(oracle_lib, oattrs, cam_from_frame(frames[0]), S, S, 0, mode=0,
                                                                  kernel_size=rend.pipe.kernel_size, bg=(1.0, 1.0, 1.0), tight=not upstream))
         n_dev = int(out["num_rendered"][0])
@@ -479,6 +489,8 @@ def test_live_shape_camera_batch_matches_oracle(cuda, oracle_lib, bin_algo):
     medium, huge = R.sort_class_counts(cuda)
     took_shared = int(_lib.lib().gvf_rast_shared_activation_calls()) - before
     assert (took_shared >= 1) == (bin_algo == "bucket") and medium > 0
+    plan = R.call_plan(st, frames, P, gm.get_features.shape[1], out["max_rendered"])
+    assert bool(plan.shared) == (took_shared >= 1) and plan.slot_mode == plan.shared and plan.order_tiles == 1
     for f in (range(len(views)) if bin_algo == "bucket" else (1,)):                # (the radix run: one frame of the call)
         ref = cached(("live", views[f], False), lambda: oracle_render(oracle_lib, oattrs, cam_from_frame(frames[f]), S, S, 0, mode=0,
                                                                       kernel_size=rend.pipe.kernel_size, bg=(1.0, 1.0, 1.0), tight=True))

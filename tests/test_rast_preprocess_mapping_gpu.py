@@ -1,6 +1,6 @@
 """The two workgroup mappings of the fused preprocess launch give the same bits -- needs an MI355X.
 
-Bucket binning without shared activation runs preprocess_kernel<false, true> (rast.hip): a workgroup owns 64 consecutive Gaussians, stages their
+Bucket binning without shared activation runs preprocess_kernel<false, true> (rast_front.hip): a workgroup owns 64 consecutive Gaussians, stages their
 SH rows once and its four waves walk different frames (wave w: frames 4 G by + w + 4 ff, G = PRE_WAVE_FB).  GVF_RAST_PRE_WAVE_FRAMES=0 puts the
 call back on preprocess_kernel<false> (256 Gaussians per workgroup, four frames in turn), which the radix binning always takes.  Both run the
 same per-Gaussian functions in the same order, so every output must be equal bit for bit.  The shapes are the smallest at which the mapping can
@@ -18,7 +18,7 @@ from rast_util import camera_block, oracle_render, compare_images, cam_from_fram
 
 pytestmark = pytest.mark.gpu
 
-PRE_WAVE_FB = 6                     # csrc/rast.hip: frames per wave of the wave-frames mapping, 4 * PRE_WAVE_FB per workgroup
+PRE_WAVE_FB = 6                     # csrc/rast_plan.h: frames per wave of the wave-frames mapping, 4 * PRE_WAVE_FB per workgroup
 KEYS = ("color", "alpha", "depth", "radii", "num_rendered")
 
 
@@ -52,6 +52,12 @@ def _render(gm, delta, frames, S, deg, wave_frames, bin_algo=None):
         out = R.rasterize_batched(st, frames, gm.activation_struct(), *raw, delta=delta, want_alpha_depth=True, want_radii=True)
         torch.cuda.synchronize()
         assert int(_lib.lib().gvf_rast_shared_activation_calls()) == before, "the call did not take the fused launch"
+        # the call plan (host only, same switches): the fused launch on the mapping the switch selects -- the radix binning always on the
+        # 256-Gaussian one --, the index-ordered count pass (at most 64 tiles here) and, with a Morton order, the gathering bin passes
+        P, bucket = gm._xyz.shape[0], st.bin_algo != _lib.RAST_BIN_RADIX
+        plan = R.call_plan(st, frames, P, raw[1].shape[1], out["max_rendered"])
+        assert plan.shared == 0 and plan.wave_frames == int(wave_frames and bucket) and plan.index_count == int(bucket)
+        assert plan.rec_gather == plan.morton == int(bucket and len(frames) >= 4 and P >= 4096)
     finally:
         for k, v in old.items():
             if v is None:
