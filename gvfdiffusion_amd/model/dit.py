@@ -26,6 +26,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import dit_plan
 from .attention import MultiHeadAttention
 from ..ops import dit_ops, precision
 from .. import _lib
@@ -200,32 +201,35 @@ class DiT(nn.Module):
         self.static_cond_proj = nn.Linear(static_cond_channels, model_channels)
         self.image_cond_proj = nn.Linear(image_cond_channels, model_channels)
         self.initialize_weights()
+        self._geom = dit_plan.DiTGeometry(C=model_channels, H=self.num_heads, head_dim=self.head_dim, Cin=in_channels, Cout=out_channels,
+                                          hidden=int(model_channels * mlp_ratio), fdim=self.t_embedder.frequency_embedding_size,
+                                          n_blocks=num_blocks, no_temporal_attn=no_temporal_attn)
         self._wcache = None       # 16-bit weights, rebuilt when any parameter (or the compute dtype) changes
         self.compute_dtype = None # None: ops/precision.py decides per forward (GVF_DIT_DTYPE, autocast, use_fp16 -> fp16 else bf16)
         self._ctx_cache = {}      # step-invariant condition products
         self.use_graph = False    # replay the whole forward as one hipGraph (set by enable_graph)
         self.train_forward = False  # forward() under grad = the differentiable forward (set by enable_training)
         self.train_linear = "torch" # route of the block projections in the differentiable forward (enable_training(linear=...))
-        import os
-        # LayerNorm folded into the GEMMs (see _forward): 0 = off (default), 1 = every projection, 2 = only the narrow ones
+        sw = dit_plan.DiTSwitches.from_env()     # the path switches: the attributes below are the writable record, read by every forward_plan
+        # LayerNorm folded into the GEMMs (_blocks_unfused): 0 = off (default), 1 = every projection, 2 = only the narrow ones
         # (N <= 512).  Built, bit-checked (tests/test_dit_gpu.py::test_layernorm_folded_into_the_gemms) and measured on the
         # denoise step: 7.35-7.49 / 7.67-7.91 / 7.35-7.48 ms per NFE for 0 / 1 / 2 -- the register-staged, re-normalised A
         # operand costs the wide projections (12-16 column tiles re-normalise the same rows) more than the LayerNorm pass it
         # removes (to_qkv 36.6 + 9.1 -> 50.7 us, mlp.0 50 + 9.1 -> 64.4 us; to_q 15.8 + 9.1 -> 20.7 us), and the statistics
         # add 2.4 us to every residual GEMM.
-        self.fuse_layernorm = int(os.environ.get("GVF_DIT_FUSE_LN", "0"))
-        # one launch per sub-layer boundary (csrc/rowblock.hip) where the shapes allow it: 0 = the unfused GEMM / LayerNorm launches
-        self.use_rowblock = int(os.environ.get("GVF_DIT_ROWBLOCK", "1")) != 0
-        self.weight_prefetch = int(os.environ.get("GVF_DIT_PREFETCH", "1")) != 0
+        self.fuse_layernorm = sw.fuse_ln
+        # one launch per sub-layer boundary (csrc/rowblock.hip) where the shapes allow it: off = the unfused GEMM / LayerNorm launches
+        self.use_rowblock = sw.rowblock
+        self.weight_prefetch = sw.prefetch
         # precompute_modulation: on (GVF_DIT_MODTABLE=0 switches it off).  4.84-4.86 ms per step with the table against 4.88-4.89 without (two alternating
         # repeats on one box).  It first measured 0.35 ms SLOWER (profiles/r04_modtable_ab.txt) -- under the sampler that still ran in lock-step with
         # the device, which paid the table's host-side lookup on the critical path.
-        self.modulation_table = int(os.environ.get("GVF_DIT_MODTABLE", "1")) != 0
+        self.modulation_table = sw.modtable
         self._fallbacks = None         # device int32 (1,): count_attention_fallbacks()
-        self.rowblock_tiled_kv = int(os.environ.get("GVF_DIT_TILED_KV", "1")) != 0    # to_qkv's launch writes the attention's K / V^T tiles itself
+        self.rowblock_tiled_kv = sw.tiled_kv      # to_qkv's launch writes the attention's K / V^T tiles itself
         # the temporal self attention runs INSIDE the row-block launch between the spatial and the image attention (T | 48): 6 launches per
         # block instead of 8, the qkv / attention-output buffers of the temporal sub-layer never exist
-        self.rowblock_temporal = int(os.environ.get("GVF_DIT_TEMPORAL_FUSED", "1")) != 0
+        self.rowblock_temporal = sw.temporal_fused
         self._graph = None
         self.capture_blocks = None     # diagnostics: a list -> _blocks_rowblock appends a copy of the fp32 stream after every block
 
@@ -334,10 +338,8 @@ class DiT(nn.Module):
         W["input_f32"] = (W["input_f32"][0].t().contiguous(), W["input_f32"][1])          # (Cin, C): the kernel copies it straight into LDS
         W["t0_f32"], W["t2_f32"] = prep32(self.t_embedder.mlp[0]), prep32(self.t_embedder.mlp[2])
         W["img_f32"], W["static_f32"] = prep32(self.image_cond_proj), prep32(self.static_cond_proj)
-        W["input"] = prep(self.input_layer)
-        W["t0"], W["t2"] = prep(self.t_embedder.mlp[0]), prep(self.t_embedder.mlp[2])
-        W["img"], W["static"] = prep(self.image_cond_proj), prep(self.static_cond_proj)
-        W["final"] = prep(self.final_layer.linear)
+        if not self._geom.small_f32:        # the 16-bit GEMM route of the two small projections (_blocks_unfused)
+            W["input"], W["final"] = prep(self.input_layer), prep(self.final_layer.linear)
         # all adaLN projections of a step as one GEMM: rows = [blk0: 6C | 3C, blk1: ..., final: 2C]
         mods_w, mods_b, offs, o = [], [], [], 0
         for blk in self.blocks:
@@ -351,7 +353,9 @@ class DiT(nn.Module):
         mods_w.append(self.final_layer.adaLN_modulation[-1].weight.detach().float())
         mods_b.append(self.final_layer.adaLN_modulation[-1].bias.detach().float())
         W["mod_w_f32"] = torch.cat(mods_w).contiguous()
-        W["mod_w"] = dit_ops.cast_pad(W["mod_w_f32"], dit_ops.pad64(self.model_channels), dtype=lp)
+        if not self._geom.mod_f32:          # the three-GEMM route of the modulation (_modulation)
+            W["t0"], W["t2"] = prep(self.t_embedder.mlp[0]), prep(self.t_embedder.mlp[2])
+            W["mod_w"] = dit_ops.cast_pad(W["mod_w_f32"], dit_ops.pad64(self.model_channels), dtype=lp)
         W["mod_b"] = torch.cat(mods_b).contiguous()
         W["mod_offs"], W["mod_total"] = offs, W["mod_b"].numel()
         W["blocks"] = []
@@ -374,30 +378,32 @@ class DiT(nn.Module):
         self._ctx_cache = {}
         return W
 
-    def _rowblock_streams(self, W):
-        """Packed weight streams of the row-block launches (csrc/rowblock.hip), built once per weight version: every launch reads ONE
-        stream -- the projection that closes a sub-layer, [the MLP,] the projection that opens the next one -- in the order it consumes
-        it.  Same 16-bit values as W's plain copies."""
-        if "rb" in W:
-            return W["rb"]
+    def _rowblock_streams(self, W, names):
+        """Packed weight streams of the row-block launches (csrc/rowblock.hip): every launch reads ONE stream -- the projection that closes
+        a sub-layer, [the MLP,] the projection that opens the next one -- in the order it consumes it.  Same 16-bit values as W's plain
+        copies.  A stream is packed, for every block, the first time a plan names it (`names`: ForwardPlan.streams) and kept in the weight
+        cache: a model whose switches change later gets the missing ones then."""
         P = dit_ops.rowblock_pack_stream
         blocks = W["blocks"]
-        first = "spatial_self_attn"
-        rb = {"in": P(None, w3=blocks[0][first]["qkv"][0]), "blocks": []}        # input_layer itself runs in fp32 (csrc/elem.hip)
-        for i, b in enumerate(blocks):
-            nxt = blocks[i + 1][first]["qkv"][0] if i + 1 < len(blocks) else None
-            d = {}
-            if self.no_temporal_attn:
-                d["s2"] = P(b["spatial_self_attn"]["out"][0], w3=b["image_cross_attn"]["q"][0])
-            else:
-                d["s2"] = P(b["spatial_self_attn"]["out"][0], w3=b["temporal_self_attn"]["qkv"][0])
-                d["s3"] = P(b["temporal_self_attn"]["out"][0], w3=b["image_cross_attn"]["q"][0])
-                d["s23"] = P(b["spatial_self_attn"]["out"][0], temporal=(b["temporal_self_attn"]["qkv"][0], b["temporal_self_attn"]["out"][0]),
-                             w3=b["image_cross_attn"]["q"][0])
-            d["s4"] = P(b["image_cross_attn"]["out"][0], w3=b["static_cross_attn"]["q"][0])
-            d["s5"] = P(b["static_cross_attn"]["out"][0], mlp=(b["fc1"][0], b["fc2"][0]), w3=nxt)
-            rb["blocks"].append(d)
-        W["rb"] = rb
+        rb = W.get("rb")
+        if rb is None:                                                            # input_layer itself runs in fp32 (csrc/elem.hip)
+            rb = W["rb"] = {"in": P(None, w3=blocks[0]["spatial_self_attn"]["qkv"][0]), "blocks": [{} for _ in blocks]}
+        for i, (b, have) in enumerate(zip(blocks, rb["blocks"])):
+            for name in names:
+                if name in have:
+                    continue
+                sp, tm, im, st = (b.get(k) for k in ("spatial_self_attn", "temporal_self_attn", "image_cross_attn", "static_cross_attn"))
+                if name == "s2":
+                    have[name] = P(sp["out"][0], w3=(im["q"] if self.no_temporal_attn else tm["qkv"])[0])
+                elif name == "s3":
+                    have[name] = P(tm["out"][0], w3=im["q"][0])
+                elif name == "s23":
+                    have[name] = P(sp["out"][0], temporal=(tm["qkv"][0], tm["out"][0]), w3=im["q"][0])
+                elif name == "s4":
+                    have[name] = P(im["out"][0], w3=st["q"][0])
+                else:
+                    assert name == "s5", name
+                    have[name] = P(st["out"][0], mlp=(b["fc1"][0], b["fc2"][0]), w3=blocks[i + 1]["spatial_self_attn"]["qkv"][0] if i + 1 < len(blocks) else None)
         return rb
 
     # ---- step-invariant condition products ------------------------------------------------------------
@@ -570,18 +576,14 @@ class DiT(nn.Module):
         fp32 projection weights cross HBM once per sample instead of once per step.  Same kernels, same numbers; any other call computes the
         modulation inside the forward as before."""
         dev = next(self.parameters()).device
-        if dev.type != "cuda" or not self.modulation_table:
+        if dev.type != "cuda" or not self.modulation_table or not self._geom.mod_f32:       # (the table is built on the fp32 route only)
             return
         W = self._weights()
-        fdim, C = self.t_embedder.frequency_embedding_size, self.model_channels
-        if not (fdim % 4 == 0 and fdim <= 1024 and C % 4 == 0 and C <= 1024):
-            return
         th = t.detach().reshape(-1).float().cpu()
         tab = getattr(self, "_mod_table", None)
         if tab is not None and tab["version"] == (self._param_version(), self._lp()) and all(float(v) in tab["rows"] for v in th.tolist()):
             return                                     # the same grid as the last sample's: the table is a per-JOB cost (~12 ms for 33 rows), not per sample
-        s2 = dit_ops.timestep_embed_f32(th.to(dev).contiguous(), *W["t0_f32"], *W["t2_f32"], freq_dim=fdim)
-        mod = dit_ops.modulation_f32(s2, W["mod_w_f32"], W["mod_b"])
+        mod = self._modulation(W, th.to(dev), True)
         self._mod_table = {"version": (self._param_version(), self._lp()), "rows": {float(v): i for i, v in enumerate(th.tolist())}, "mod": mod,
                            "arange": torch.arange(mod.shape[0], device=dev)}
 
@@ -599,6 +601,23 @@ class DiT(nn.Module):
         if all(i == idx[0] for i in idx):
             return tab["arange"][idx[0]:idx[0] + 1].expand(B)
         return tab["arange"][torch.tensor(idx)]
+
+    def _modulation(self, W, t, mod_f32):
+        """(K, mod_total) fp32: the timestep embedder (sinusoid, two Linears, two SiLUs) and every adaLN projection of the step for the K
+        times in `t` (on the device).  mod_f32 (ForwardPlan.mod_f32): one launch + one GEMV, both in fp32; otherwise three 16-bit GEMMs."""
+        fdim, C, bf = self.t_embedder.frequency_embedding_size, self.model_channels, W["lp"]
+        if mod_f32:
+            s2 = dit_ops.timestep_embed_f32(t.float().contiguous(), *W["t0_f32"], *W["t2_f32"], freq_dim=fdim)
+            return dit_ops.modulation_f32(s2, W["mod_w_f32"], W["mod_b"])
+        K, f32 = t.shape[0], torch.float32
+        mod = torch.empty((K, W["mod_total"]), dtype=f32, device=t.device)
+        tf = dit_ops.cast_pad(TimestepEmbedder.timestep_embedding(t, fdim).contiguous(), dit_ops.pad64(fdim), dtype=bf)
+        h1 = torch.empty((K, C), dtype=f32, device=t.device)
+        dit_ops.gemm(tf, *W["t0"], h1, dit_ops.EPI_STORE_F32)
+        t_emb = torch.empty((K, C), dtype=f32, device=t.device)
+        dit_ops.gemm(dit_ops.cast_pad(h1, dit_ops.pad64(C), act=1, dtype=bf), *W["t2"], t_emb, dit_ops.EPI_STORE_F32)
+        dit_ops.gemm(dit_ops.cast_pad(t_emb, dit_ops.pad64(C), act=1, dtype=bf), W["mod_w"], W["mod_b"], mod, dit_ops.EPI_STORE_F32)
+        return mod
 
     def count_attention_fallbacks(self, on: bool = True):
         """Instrument the tiled attention launches (spatial self, image cross, static cross: 3 per block) with the C ABI's `fallback_counter`
@@ -623,7 +642,15 @@ class DiT(nn.Module):
         return n
 
     def attention_workgroups(self, B: int, T: int, N: int) -> int:
-        return len(self.blocks) * 3 * B * T * self.num_heads * ((N + 255) // 256)
+        return self.forward_plan(B, T, N).attention_workgroups
+
+    # ---- which launches a forward makes ---------------------------------------------------------------------
+    def forward_plan(self, B: int, T: int, N: int) -> dit_plan.ForwardPlan:
+        """The launches a forward of x (B, T, N, in_channels) makes under the switches as they stand now (dit_plan.plan_forward, memoised
+        there).  Host code only: works on a CPU model."""
+        sw = dit_plan.DiTSwitches(rowblock=bool(self.use_rowblock), tiled_kv=bool(self.rowblock_tiled_kv), temporal_fused=bool(self.rowblock_temporal),
+                                  prefetch=bool(self.weight_prefetch), fuse_ln=int(self.fuse_layernorm), modtable=bool(self.modulation_table))
+        return dit_plan.plan_forward(self._geom, sw, B, T, N)
 
     # ---- forward ------------------------------------------------------------------------------------------
     def forward(self, x: torch.Tensor, t: torch.Tensor, cond_images: torch.Tensor, static_latent: torch.Tensor,
@@ -669,8 +696,9 @@ class DiT(nn.Module):
         # here, eagerly, INTO the buffers the captured graph reads (prepare_conditions keeps them per shape: `epoch`), so the graph is replayed
         # for sample after sample and re-captured only when the buffer set itself changes (another shape, operand type or weight version)
         ctx = self.prepare_conditions(cond_images, static_latent, deformation_position_xyz, x.shape[1])
+        # the plan is part of the key: a path switch assigned between two forwards is a re-capture, not a replay of the other path
         key = (tuple(x.shape), x.dtype, tuple(t.shape), t.dtype, pv, self._lp(),
-               None if mod_rows is None else self._mod_table["mod"].data_ptr(), ctx["epoch"])
+               None if mod_rows is None else self._mod_table["mod"].data_ptr(), ctx["epoch"], self.forward_plan(*x.shape[:3]))
         conds = (cond_images, static_latent, deformation_position_xyz)
         g = self._graph
         if g is None or g["key"] != key:
@@ -705,65 +733,49 @@ class DiT(nn.Module):
         """mod_idx: optional (B,) row numbers into precompute_modulation's table (the graphed forward hands its static copy in)."""
         _lib.require_cuda(x, t, cond_images, static_latent, deformation_position_xyz)
         B, T, N, Cin = x.shape
-        C, H = self.model_channels, self.num_heads
-        dev = x.device
-        M = B * T * N
         W = self._weights()
         ctx = self.prepare_conditions(cond_images, static_latent, deformation_position_xyz, T)
-        Li, Ls = ctx["Li"], ctx["Ls"]
-        bf, f32 = W["lp"], torch.float32              # bf: the 16-bit operand type of this forward (bf16 or fp16)
-
-        # timestep embedder (sinusoid, two Linears, two SiLUs: one launch) and every adaLN projection of the step (one GEMV), both in fp32
-        fdim = self.t_embedder.frequency_embedding_size
+        plan = self.forward_plan(B, T, N)
         if mod_idx is None and not self.use_graph:
             mod_idx = self._mod_from_table(t, B)           # eager calls look the step up here (the graphed forward hands its copy in)
         if mod_idx is not None:
             mod = self._mod_table["mod"].index_select(0, mod_idx)
-            assert mod.shape == (B, W["mod_total"]) and mod.dtype == f32
-        elif fdim % 4 == 0 and fdim <= 1024 and C % 4 == 0 and C <= 1024:
-            s2 = dit_ops.timestep_embed_f32(t.to(dev).float().contiguous(), *W["t0_f32"], *W["t2_f32"], freq_dim=fdim)
-            mod = dit_ops.modulation_f32(s2, W["mod_w_f32"], W["mod_b"])
+            assert mod.shape == (B, W["mod_total"]) and mod.dtype == torch.float32
         else:
-            mod = torch.empty((B, W["mod_total"]), dtype=f32, device=dev)
-            tf = dit_ops.cast_pad(TimestepEmbedder.timestep_embedding(t.to(dev), fdim).contiguous(), dit_ops.pad64(fdim), dtype=bf)
-            h1 = torch.empty((B, C), dtype=f32, device=dev)
-            dit_ops.gemm(tf, *W["t0"], h1, dit_ops.EPI_STORE_F32)
-            t_emb = torch.empty((B, C), dtype=f32, device=dev)
-            dit_ops.gemm(dit_ops.cast_pad(h1, dit_ops.pad64(C), act=1, dtype=bf), *W["t2"], t_emb, dit_ops.EPI_STORE_F32)
-            dit_ops.gemm(dit_ops.cast_pad(t_emb, dit_ops.pad64(C), act=1, dtype=bf), W["mod_w"], W["mod_b"], mod, dit_ops.EPI_STORE_F32)
-        mod_ld = W["mod_total"]
+            mod = self._modulation(W, t.to(x.device), plan.mod_f32)
+        x2d = x.reshape(B * T * N, Cin).float().contiguous()
+        pos = None if ctx["pos"] is None else ctx["pos"].reshape(B * N, self.model_channels)
+        y = (self._blocks_rowblock if plan.path == "rowblock" else self._blocks_unfused)(plan, x2d, mod, W, ctx, B, T, N, pos)
+        return y.reshape(B, T, N, self.out_channels).to(x.dtype if x.dtype.is_floating_point else torch.float32)
 
+    def _blocks_unfused(self, plan, x2d, mod, W, ctx, B, T, N, pos):
+        """The blocks with one launch per GEMM, LayerNorm and attention (csrc/gemm.hip, elem.hip, attn.hip, attn_xt.hip): every shape the
+        row-block launches do not cover.  Returns y (B T N, out_channels) fp32."""
+        C, H, hd = self.model_channels, self.num_heads, self.head_dim
+        dev = x2d.device
+        M, TN = plan.M, plan.TN
+        Li, Ls = ctx["Li"], ctx["Ls"]
+        bf, f32 = W["lp"], torch.float32              # bf: the 16-bit operand type of this forward (bf16 or fp16)
+        mod_ld = W["mod_total"]
+        small_f32 = plan.small_f32
         # residual stream h (fp32) = position embedding broadcast over T + input_layer(x), in fp32 (csrc/elem.hip)
-        small_f32 = C <= 512 and C % 4 == 0 and Cin <= 24 and self.out_channels <= 32
-        x2d = x.reshape(M, Cin).float().contiguous()
-        pos = None if ctx["pos"] is None else ctx["pos"].reshape(B * N, C)
-        # the row-block launches work on whole 48-row blocks of one sample: a sample whose T * N is not a multiple of 48 (T = 16, 32 at
-        # N = 512) gets its rows padded (needs whole 64-key tiles per frame for the attention's strided views: N % 64 == 0)
-        TNp = dit_ops.rowblock_padded_rows(T * N)
-        if self.use_rowblock and self.head_dim == 32 and small_f32 and Cin % 4 == 0 and Cin <= 16 and dit_ops.rowblock_supported(C, TNp, int(C * self.mlp_ratio)) \
-                and (TNp == T * N or (N % 64 == 0 and self.rowblock_tiled_kv)):
-            y = self._blocks_rowblock(x2d, mod, mod_ld, W, ctx, B, T, N, pos)          # its first launch also does input_layer
-            return y.to(x.dtype if x.dtype.is_floating_point else f32)
         h = torch.empty((M, C), dtype=f32, device=dev)
         if small_f32:
-            dit_ops.input_layer_f32(x2d, W["input_f32"][0], W["input_f32"][1], h, pos=pos, pos_period=N, rows_per_group=T * N)
+            dit_ops.input_layer_f32(x2d, W["input_f32"][0], W["input_f32"][1], h, pos=pos, pos_period=N, rows_per_group=TN)
         elif ctx["pos"] is not None:
             h.copy_(ctx["pos"][:, None].expand(B, T, N, C).reshape(M, C))
         else:
             h.zero_()
-        xb = None if small_f32 else dit_ops.cast_pad(x.reshape(M, Cin).float().contiguous(), dit_ops.pad64(Cin), dtype=bf)
+        xb = None if small_f32 else dit_ops.cast_pad(x2d, dit_ops.pad64(x2d.shape[1]), dtype=bf)
         hb = torch.empty((M, C), dtype=bf, device=dev)          # attention-output scratch of the cross attentions
         qkv = torch.empty((M, 3 * C), dtype=bf, device=dev)
         ab = torch.empty((M, C), dtype=bf, device=dev)          # attention output / q projection
         hidden = torch.empty((M, int(C * self.mlp_ratio)), dtype=bf, device=dev)
-        TN = T * N
-        hd = self.head_dim
         nb_self = B * T * H * ((N + 63) // 64) * 4096
         kv_self = (torch.empty(nb_self, dtype=torch.uint8, device=dev), torch.empty(nb_self, dtype=torch.uint8, device=dev))
         # LayerNorm is folded into the GEMMs around it (csrc/gemm.hip): every update of the stream x = x + g * h also writes
         # the row statistics of the new x, and the projection that follows normalises its A operand on the fly
-        fuse_ln = self.fuse_layernorm != 0 and TN % 128 == 0 and C % 128 == 0 and C <= 1024
-        fuse_max_n = 1 << 30 if self.fuse_layernorm == 1 else 512
+        fuse_ln, fuse_max_n = plan.fuse_ln, plan.fuse_max_n
         n_part = dit_ops.gemm_stats_parts(C)
         stats = torch.empty((M, n_part, 2), dtype=f32, device=dev) if fuse_ln else None
         have_stats = [False]       # the row statistics exist once a residual GEMM has written them: the fp32 input layer (csrc/elem.hip) does
@@ -798,7 +810,7 @@ class DiT(nn.Module):
             # -- spatial self attention over N
             a = b["spatial_self_attn"]
             ln_gemm(a["qkv"], qkv, dit_ops.EPI_STORE_16, shift=sh_s, scale=sc_s)
-            if hd != 32:
+            if plan.strided_attention:
                 s3 = (N * 3 * C, 0, 3 * C)
                 dit_ops.attention(qkv, qkv[:, C:], qkv[:, 2 * C:], ab, B * T, 1, N, N, H, s3, s3, s3, (N * C, 0, C), a["gq"], a["gk"], head_dim=hd)
             else:
@@ -818,7 +830,7 @@ class DiT(nn.Module):
             # -- image cross attention (affine LayerNorm, cached K/V)
             a = b["image_cross_attn"]
             ln_gemm(a["q"], ab, dit_ops.EPI_STORE_16, ln_w=b["n3"][0], ln_b=b["n3"][1])
-            if hd != 32:
+            if plan.strided_attention:
                 kv = ctx["kv_img"][i]                             # (B T Li, 2C) rows [k | v], one key set per (sample, frame)
                 sk = (Li * 2 * C, 0, 2 * C)
                 dit_ops.attention(ab, kv, kv[:, C:], hb, B * T, 1, N, Li, H, (N * C, 0, C), sk, sk, (N * C, 0, C), a["gq"], a["gk"], head_dim=hd)
@@ -829,7 +841,7 @@ class DiT(nn.Module):
             # -- static cross attention: K/V shared by the T frames of a sample (inner stride 0)
             a = b["static_cross_attn"]
             ln_gemm(a["q"], ab, dit_ops.EPI_STORE_16, ln_w=b["n4"][0], ln_b=b["n4"][1])
-            if hd != 32:
+            if plan.strided_attention:
                 kv = ctx["kv_st"][i]                              # (B Ls, 2C): one key set per sample, shared by its T frames (inner stride 0)
                 sk = (Ls * 2 * C, 0, 2 * C)
                 dit_ops.attention(ab, kv, kv[:, C:], hb, B, T, N, Ls, H, (TN * C, N * C, C), sk, sk, (TN * C, N * C, C), a["gq"], a["gk"], head_dim=hd)
@@ -847,9 +859,9 @@ class DiT(nn.Module):
             dit_ops.final_layer_f32(h, W["final_f32"][0], W["final_f32"][1], y, shift=mview(o), scale=mview(o + C), mod_ld=mod_ld, rows_per_group=TN)
         else:
             ln_gemm(W["final"], y, dit_ops.EPI_STORE_F32, shift=mview(o), scale=mview(o + C))
-        return y.reshape(B, T, N, self.out_channels).to(x.dtype if x.dtype.is_floating_point else f32)
+        return y
 
-    def _blocks_rowblock(self, x2d, mod, mod_ld, W, ctx, B, T, N, pos):
+    def _blocks_rowblock(self, plan, x2d, mod, W, ctx, B, T, N, pos):
         """The blocks with one launch per sub-layer boundary (csrc/rowblock.hip): per block  spatial attention | to_out + adaLN +
         to_qkv | temporal attention | to_out + norm3 + to_q | image attention | to_out + norm4 + to_q | static attention | to_out +
         adaLN + MLP + adaLN + the NEXT block's to_qkv (q row-major, K / V^T as the attention's tile images) -- 8 launches instead of 20, the fp32 stream through HBM 5 times instead of 15,
@@ -857,13 +869,12 @@ class DiT(nn.Module):
         Row layout: sample b owns rows [b TNp, b TNp + T N), TNp = T N rounded up to whole 48-row blocks; the padding rows (T N not a
         multiple of 48) are computed like any other row by the row-block launches and never read by an attention."""
         C, H = self.model_channels, self.num_heads
-        TN = T * N
-        TNp = dit_ops.rowblock_padded_rows(TN)
-        padded = TNp != TN
-        M = B * TNp
+        TN, TNp, padded, M = plan.TN, plan.TNp, plan.padded, plan.M
+        tiled_kv, temporal_fused, fr = plan.tiled_kv, plan.temporal_fused, plan.frames
         dev = x2d.device
         bf, f32 = W["lp"], torch.float32              # bf: the 16-bit operand type (bf16 or fp16); the packed streams are of that type
-        rb = self._rowblock_streams(W)
+        mod_ld = W["mod_total"]
+        rb = self._rowblock_streams(W, plan.streams)
         Li, Ls = ctx["Li"], ctx["Ls"]
         # buffers an attention writes and a row-block launch reads whole: their padding rows must stay finite
         alloc = torch.zeros if padded else torch.empty
@@ -891,16 +902,11 @@ class DiT(nn.Module):
         # every attention launch also touches the packed weights of the row-block launch behind it (GVF_DIT_PREFETCH=0: off): the 107 MB of
         # weights of a forward cycle through the caches once per step, so each launch starts on cold weights -- while the attention before it,
         # bound by its matrix / vector pipes, leaves the memory system idle
-        pf = (lambda t: t) if self.weight_prefetch else (lambda t: None)
+        pf = (lambda s, name: s[name]) if plan.prefetch else (lambda s, name: None)
 
         o = offs[0]
-        # h = pos + input_layer(x); adaLN of block 0; its to_qkv
-        # to_qkv of the spatial self attention: with whole 64-key tiles per frame its launch writes q row-major and K / V^T directly as the
-        # tiled images the attention kernel stages (no row-major k, v; no pack launch)
-        tiled_kv = N % 64 == 0 and self.rowblock_tiled_kv
-        R = dit_ops.ROWBLOCK_ROWS
-        # (a padded sample's padding rows are exactly the phantom tokens of its last block: ceil(N / (R / T)) * R == TNp)
-        temporal_fused = self.rowblock_temporal and not self.no_temporal_attn and R % T == 0
+        # to_qkv of the spatial self attention: with whole 64-key tiles per frame (plan.tiled_kv) its launch writes q row-major and K / V^T
+        # directly as the tiled images the attention kernel stages (no row-major k, v; no pack launch)
         qs = torch.empty((M, C), dtype=bf, device=dev) if tiled_kv else None
 
         def qkv_out(blk):
@@ -908,14 +914,6 @@ class DiT(nn.Module):
             if tiled_kv:
                 return dict(out3=qs, b3=a_["qkv"][1], kv_tiles=kv_self, kv_L=N, gamma_k=a_["gk"], kv_group_rows=TN if padded else 0)
             return dict(out3=qkv, b3=a_["qkv"][1])
-
-        # per-frame views of the row buffers.  Padded: outer = sample (stride TNp rows), inner = frame (N rows), key set of (b, f) = b T + f;
-        # otherwise the frames of all samples are one uniform run (the launch geometry the kernels were tuned on)
-        if padded:
-            fr = dict(n=(B, T), c=(TNp * C, N * C, C), c3=(TNp * 3 * C, N * 3 * C, 3 * C), kv=(T, 1))
-        else:
-            fr = dict(n=(B * T, 1), c=(N * C, 0, C), c3=(N * 3 * C, 0, 3 * C), kv=(1, 0))
-        fr_c = (TNp * C, N * C, C)                                 # (sample, frame) view for the per-sample key set of the static attention
 
         # h = pos (broadcast over the frames) + input_layer(x) in fp32, adaLN of block 0 and its to_qkv: one launch
         if pos is None:
@@ -928,11 +926,11 @@ class DiT(nn.Module):
             n3, n4 = dict(ln_w=b["n3"][0], ln_b=b["n3"][1]), dict(ln_w=b["n4"][0], ln_b=b["n4"][1])
             a = b["spatial_self_attn"]
             if tiled_kv:
-                dit_ops.attention_tiled(qs, kv_self[0], kv_self[1], ab, *fr["n"], N, N, H, fr["c"], fr["c"], *fr["kv"], gamma_q=a["gq"], bounded=a["bounded"], fallback_counter=self._fallbacks,
-                                        prefetch=pf(s["s23"] if (temporal_fused and not self.no_temporal_attn) else s["s2"]))
-            else:                                              # (never padded: see _forward)
+                dit_ops.attention_tiled(qs, kv_self[0], kv_self[1], ab, *fr.n, N, N, H, fr.c, fr.c, *fr.kv, gamma_q=a["gq"], bounded=a["bounded"], fallback_counter=self._fallbacks,
+                                        prefetch=pf(s, plan.spatial_prefetch_stream))
+            else:                                              # (never padded: dit_plan.plan_forward)
                 dit_ops.attention_pack_kv(qkv, B * T, N, H, C, 2 * C, gamma_k=a["gk"], out=kv_self)
-                dit_ops.attention_tiled(qkv, kv_self[0], kv_self[1], ab, *fr["n"], N, N, H, fr["c3"], fr["c"], *fr["kv"], gamma_q=a["gq"], bounded=a["bounded"], fallback_counter=self._fallbacks)
+                dit_ops.attention_tiled(qkv, kv_self[0], kv_self[1], ab, *fr.n, N, N, H, fr.c3, fr.c, *fr.kv, gamma_q=a["gq"], bounded=a["bounded"], fallback_counter=self._fallbacks)
             ai = b["image_cross_attn"]
             if self.no_temporal_attn:
                 fused(ab, s["s2"], b1=a["out"][1], gate1=g_s, ln1=n3, out3=qb, b3=ai["q"][1])
@@ -948,11 +946,11 @@ class DiT(nn.Module):
                     dit_ops.attention(qkv, qkv[:, C:], qkv[:, 2 * C:], ab, B, N, T, T, H, st, st, st, (TNp * C, C, N * C), at["gq"], at["gk"])
                     fused(ab, s["s3"], b1=at["out"][1], gate1=g_t, ln1=n3, out3=qb, b3=ai["q"][1])
             kt, vt = ctx["kv_img"][i]
-            dit_ops.attention_tiled(qb, kt, vt, hb, *fr["n"], N, Li, H, fr["c"], fr["c"], *fr["kv"], gamma_q=ai["gq"], bounded=ai["bounded"], fallback_counter=self._fallbacks, prefetch=pf(s["s4"]))
+            dit_ops.attention_tiled(qb, kt, vt, hb, *fr.n, N, Li, H, fr.c, fr.c, *fr.kv, gamma_q=ai["gq"], bounded=ai["bounded"], fallback_counter=self._fallbacks, prefetch=pf(s, "s4"))
             ast = b["static_cross_attn"]
             fused(hb, s["s4"], b1=ai["out"][1], ln1=n4, out3=qb, b3=ast["q"][1])
             kt, vt = ctx["kv_st"][i]
-            dit_ops.attention_tiled(qb, kt, vt, hb, B, T, N, Ls, H, fr_c, fr_c, 1, 0, gamma_q=ast["gq"], bounded=ast["bounded"], fallback_counter=self._fallbacks, prefetch=pf(s["s5"]))
+            dit_ops.attention_tiled(qb, kt, vt, hb, B, T, N, Ls, H, fr.static, fr.static, 1, 0, gamma_q=ast["gq"], bounded=ast["bounded"], fallback_counter=self._fallbacks, prefetch=pf(s, "s5"))
             kw = dict(b1=ast["out"][1], ln1=dict(shift=sh_m, scale=sc_m), mlp_bias=(b["fc1"][1], b["fc2"][1]), hidden=hidden_units, gate_m=g_m)
             if i + 1 < len(blocks):
                 on = offs[i + 1]

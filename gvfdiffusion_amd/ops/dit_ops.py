@@ -264,18 +264,9 @@ def final_layer_f32(x, w, bias, out, shift=None, scale=None, mod_ld=0, rows_per_
     return out
 
 
-ROWBLOCK_C, ROWBLOCK_ROWS, ROWBLOCK_KPAD, ROWBLOCK_MAX_HIDDEN, ROWBLOCK_MAX_N3 = 512, 48, 128, 2048, 1536
-
-
-def rowblock_supported(C: int, rows_per_group: int, hidden: int) -> bool:
-    """The row-block kernel covers model_channels 512, 48-row blocks that do not straddle samples (callers pad a sample's rows to a
-    multiple of 48: rowblock_padded_rows), an MLP of <= 2048 hidden units."""
-    return C == ROWBLOCK_C and rows_per_group % ROWBLOCK_ROWS == 0 and hidden % ROWBLOCK_C == 0 and 0 < hidden <= ROWBLOCK_MAX_HIDDEN
-
-
-def rowblock_padded_rows(rows: int) -> int:
-    """Rows of a sample rounded up to whole 48-row blocks."""
-    return (rows + ROWBLOCK_ROWS - 1) // ROWBLOCK_ROWS * ROWBLOCK_ROWS
+# the row-block launch's limits have one definition, beside the rules that read them (model/dit_plan.py)
+from ..model.dit_plan import (ROWBLOCK_C, ROWBLOCK_ROWS, ROWBLOCK_KPAD, ROWBLOCK_MAX_HIDDEN, ROWBLOCK_MAX_N3,  # noqa: E402,F401
+                              rowblock_supported, rowblock_padded_rows)
 
 
 def rowblock_pack_stream(w1, mlp=None, w3=None, temporal=None):

@@ -520,7 +520,7 @@ def test_rowblock_path_batch_of_three_equals_three_single_samples(cuda):
 
 @pytest.mark.gpu
 def test_rowblock_path_of_the_dit_equals_the_unfused_path(cuda):
-    """Full-size config (C = 512, 24 x 512 tokens): DiT._blocks_rowblock against the per-sub-layer launches of DiT._forward."""
+    """Full-size config (C = 512, 24 x 512 tokens): DiT._blocks_rowblock against the per-sub-layer launches of DiT._blocks_unfused."""
     from gvfdiffusion_amd.model.dit import DiT
     man = json.load(open(os.path.join(GOLD, "dit_manifest.json")))
     net = DiT(**man["config"])
@@ -566,8 +566,9 @@ def test_rowblock_path_pads_samples_whose_rows_are_not_whole_blocks(cuda, B, T):
         y1 = net(**inp)
     finally:
         dit_ops.rowblock_fused = orig
-    per_block = 3 if dit_ops.ROWBLOCK_ROWS % T == 0 else 4                  # T | 48: the temporal attention runs inside a row-block launch
-    assert len(launches) == 1 + per_block * 2 and max(launches) == T * 512   # the padded row-block path ran
+    plan = net.forward_plan(B, T, 512)        # (T | 48: the temporal attention runs inside a row-block launch; tests/test_dit_plan_host.py has the table)
+    assert plan.path == "rowblock" and plan.padded and plan.launches["rowblock_fused"] == {16: 7, 5: 9, 8: 7}[T]
+    assert len(launches) == plan.launches["rowblock_fused"] and max(launches) == T * 512   # the padded row-block path ran
     net.use_rowblock = False
     y0 = net(**inp)
     net.use_rowblock = True
