@@ -65,6 +65,10 @@ SOURCES = {
     "dit_train.hip": [],
     # weight gradient + transposing cast: the gemm.hip flags (accumulators in VGPRs: the epilogue stores them without accvgpr reads)
     "linear_grad.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # 3x3 convolution: the gemm.hip flags (16 accumulators per wave in VGPRs, the epilogue reads them without accvgpr moves)
+    "conv3x3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # LPIPS pool and tap kernels: default flags
+    "lpips.hip": [],
 }
 
 

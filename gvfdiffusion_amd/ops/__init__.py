@@ -8,4 +8,5 @@ from . import attention_grad  # noqa: F401
 from . import optim  # noqa: F401
 from . import dit_train  # noqa: F401
 from . import linear_grad  # noqa: F401
+from . import lpips  # noqa: F401
 from ..sparse import vox2seq as _vox2seq  # noqa: F401,E402

@@ -74,17 +74,21 @@ def render_l1_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsi
 
 def render_loss_frames(renderer, gaussian, extrinsics: torch.Tensor, intrinsics: torch.Tensor, deltas: torch.Tensor,
                        targets: torch.Tensor, frame_of_view: Optional[Sequence[int]] = None, l1_weight: float = 1.0,
-                       ssim_weight: float = 0.2) -> torch.Tensor:
-    """The reference's render loss without its LPIPS term (train_vae.py:328-334):
-        l1_weight * L1(frames, targets) + ssim_weight * (1 - ssim(frames, targets))
-    over the stacked (V, 3, H, W) views, rendered in ONE renderer.render_frames call as in render_l1_loss_frames and scored by ONE
-    fused HIP loss (ops/image_loss.py: gvf_image_loss_forward / _backward).  For views of one size, the L1 over the stack equals
-    the mean of the per-view L1s of render_l1_loss_frames."""
+                       ssim_weight: float = 0.2, lpips=None, lpips_weight: float = 0.0) -> torch.Tensor:
+    """The reference's render loss (train_vae.py:328-334):
+        l1_weight * L1(frames, targets) + ssim_weight * (1 - ssim(frames, targets)) + lpips_weight * lpips(frames * 2 - 1, targets * 2 - 1)
+    over the stacked (V, 3, H, W) views, rendered in ONE renderer.render_frames call as in render_l1_loss_frames.  L1 and SSIM are ONE
+    fused HIP loss (ops/image_loss.py: gvf_image_loss_forward / _backward); the LPIPS term is added when `lpips` is an ops.lpips.LPIPS
+    module (the caller owns it and its weights) and lpips_weight is not zero -- with the defaults the loss is the L1 + SSIM part alone.
+    For views of one size, the L1 over the stack equals the mean of the per-view L1s of render_l1_loss_frames."""
     from .ops.image_loss import image_loss
     V = extrinsics.shape[0]
     index = list(range(V)) if frame_of_view is None else [int(t) for t in frame_of_view]
     imgs = renderer.render_frames(gaussian, extrinsics, intrinsics, delta_pc=deltas, delta_index=index)["rgb"]
-    return image_loss(imgs, targets, l1_weight=l1_weight, ssim_weight=ssim_weight)
+    loss = image_loss(imgs, targets, l1_weight=l1_weight, ssim_weight=ssim_weight)
+    if lpips is not None and lpips_weight != 0.0:
+        loss = loss + lpips_weight * lpips(imgs * 2 - 1, targets * 2 - 1)
+    return loss
 
 
 def interpolation_loss(static_gs: Sequence[torch.Tensor], micro_static_pc: torch.Tensor, micro_moving_pc: torch.Tensor, output: torch.Tensor,
