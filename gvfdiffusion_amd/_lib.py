@@ -75,6 +75,7 @@ SIGNATURES = {
     "gvf_rast_sort_class_counts": (_i, [_vp, _sz, _i, _i, _i, _i, _i64, ctypes.POINTER(ctypes.c_uint32), _vp]),
     "gvf_rast_call_plan": (_i, [ctypes.POINTER(GvfRastSettings), ctypes.POINTER(GvfRastFrame), _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64,
                                 ctypes.POINTER(GvfRastPlan)]),
+    "gvf_rast_bin_record_bytes": (_i, [ctypes.POINTER(GvfRastSettings), ctypes.POINTER(_i)]),
     "gvf_rast_slice_groups": (_i, [ctypes.POINTER(GvfRastFrame), _i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i)]),
     "gvf_rast_profile_enable": (_i, [_i]),
     "gvf_rast_profile_read": (_i, [ctypes.POINTER(_f), ctypes.POINTER(_i)]),

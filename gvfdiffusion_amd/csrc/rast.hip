@@ -12,7 +12,7 @@
 // Default = BUCKET binning (GvfRastSettings.bin_algo):
 //   bbox, morton_count/scan/scatter      once per call: 15-bit Morton order of the Gaussians (locality for the bin passes)
 //   preprocess   grid (ceil(P/256), F/4) activations (+deltas), EWA covariance, 2D filter, radius, tile rect, alpha-box
-//                                        instance culling, SH -> RGB; writes one 64-byte splat record + a 16-byte bin record
+//                                        instance culling, SH -> RGB; writes one 64-byte splat record + an 8- or 16-byte bin record
 //                                        (without shared activation: grid (ceil(P/64), ceil(F/24)), one frame per wave at a time)
 //   bin<count>   grid (ceil(P/1024), F)  per-(frame, tile) instance counts: LDS histogram per block, one global atomic
 //                                        per touched tile
@@ -35,9 +35,10 @@
 // so the blend's gather of a (splat, tile) instance touches exactly one cache line (three 40-B-total arrays cost
 // three lines per instance: 5.7 GB of fabric reads per 24-frame step measured with FETCH_SIZE, vs 1.1 GB
 // algorithmic); hx, hy = half extents of the region where alpha can reach 1/255 (instance and quadrant culling),
-// computed once per visible Gaussian.  A 16-byte bin record {x0|y0<<16, x1|y1<<16, depth bits, 0}; per
-// (frame, tile) a range, a counter and a cursor; per instance one u64 key and one u32 ordered id (radix path:
-// u64 key + u32 id, double buffered).
+// computed once per visible Gaussian.  A bin record (bucket binning): 8 bytes {x0|y0<<8|x1<<16|y1<<24, depth bits} when the
+// tile grid is at most 255 x 255 (images up to 4080 px either way), else 16 bytes {x0|y0<<16, x1|y1<<16, depth bits, 0}; the array
+// is carved at 16 bytes per record either way.  Per (frame, tile) a range, a counter and a cursor; per instance one u64 key and
+// one u32 ordered id (radix path: u64 key + u32 id, double buffered).
 #include <atomic>
 #include <cstdlib>
 #include <vector>
@@ -75,6 +76,7 @@ RastSwitches switches_from_env() {
     sw.slot_order = switch_on("GVF_RAST_SLOT_ORDER");
     sw.pre_wave_frames = switch_on("GVF_RAST_PRE_WAVE_FRAMES");   // 0: the bucket-binning fused launch on the 256-Gaussian mapping
     sw.blend_order = switch_on("GVF_RAST_BLEND_ORDER");
+    sw.bin_rec8 = switch_on("GVF_RAST_BIN_REC8");                 // 0: 16-byte bin records on every grid
     return sw;
 }
 
@@ -191,7 +193,7 @@ Workspace gvf_rast::carve(void* ws, size_t bytes, int P, int F, int H, int W, in
     w.order_alt = c.take<uint32_t>(Pp);
     w.mhist = c.take<uint32_t>(MORTON_BINS);
     w.mm = c.take<uint32_t>(8);
-    w.binrec = c.take<uint4>(FP);
+    w.binrec = c.take<uint4>(FP);           // 16 bytes per record whichever form the call's plan takes (the layout does not depend on it)
     w.sort_tmp_bytes = gvf_sort_tmp_bytes((int64_t)D);
     w.sort_tmp = c.take<char>(w.sort_tmp_bytes);
     w.bytes = gvf_align_up(c.off, 256);
@@ -267,6 +269,18 @@ extern "C" int gvf_rast_call_plan(const GvfRastSettings* st, const GvfRastFrame*
     in.has_delta = has_delta != 0; in.has_subpixel_offset = has_subpixel_offset != 0;
     in.max_rendered = max_rendered;
     *out = plan_call(*st, frames_host, in, switches_from_env());   // (the public part of the plan)
+    return GVF_OK;
+}
+
+// test-only diagnostic: the bin-record form a call with these settings takes (the private part of the plan), through the forward's own
+// plan_call and switches; the form does not depend on the Gaussians or the frames, so the plan is that of one frame without Gaussians
+extern "C" int gvf_rast_bin_record_bytes(const GvfRastSettings* st, int* bytes) {
+    if (!st || !bytes) return GVF_EINVAL;
+    if (check_shape(*st, 1, 0, 0) != GVF_OK) return GVF_EINVAL;
+    const GvfRastFrame frame = {};
+    PlanInputs in = {};
+    in.F = 1;
+    *bytes = plan_call(*st, &frame, in, switches_from_env()).rec8 ? 8 : 16;
     return GVF_OK;
 }
 

@@ -337,7 +337,8 @@ struct Workspace {
     uint32_t* tile_count; uint32_t* cursor;            // bucket binning: [F*ntiles] each
     uint32_t* partial;
     uint32_t* order; uint32_t* order_alt; uint32_t* mhist; uint32_t* mm;
-    uint4* binrec;                                     // [F*P] {x0|y0<<16, x1|y1<<16, depth bits, -}
+    uint4* binrec;                                     // room for [F*P] 16-byte bin records {x0|y0<<16, x1|y1<<16, depth bits, -}; a call whose
+                                                       // plan says rec8 keeps [F*P] 8-byte ones {x0|y0<<8|x1<<16|y1<<24, depth bits} in its first half
     void* sort_tmp; size_t sort_tmp_bytes;
     size_t bytes; bool ok;
 };

@@ -17,6 +17,10 @@ namespace {
 // (coalesced lines), the count pass (bin_index_kernel) walks them in index order against a whole-frame LDS tile table, and the scatter pass
 // (bin_kernel) gathers them in Morton order, each XCD taking whole frames.  Records at the Morton slot, or both passes in one order, are
 // slower (profiles/r07_bin_layout_ab.txt).  The shared-activation path keeps its records at the Morton slot.
+// The bin records come in two forms, chosen by the call's plan (RastPlan::rec8) and compiled into preprocess_kernel, bin_index_kernel and
+// bin_kernel as a template argument: 8 bytes (BinRec8) when the tile grid is at most 255 x 255, so that a rect coordinate fits 8 bits --
+// half the bytes through the stores and both passes, and a frame's records (P x 8 B) fit one XCD's L2 in the gather at P = 262144 --, else
+// 16 bytes (BinRec16).  Both hold the rect and the depth bits losslessly: the keys and counts of a call are the same either way.
 
 struct PreParams {
     int P, M, deg, H, W, mode;
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(256) void activate_cov_kernel(GvfGaussianActivation
     if (i >= P) return;
     // SLOT ORDER (slot_of != null): the record of Gaussian i goes to its Morton slot (a whole 64-byte line, scattered ONCE per slice) and slice 0's
     // workgroups also copy the SH rows into slot order; the per-frame launch then runs over slots: its record reads, its splat records and its bin
-    // records (16 bytes each, scattered to the slot by the index-ordered form: 21 % of that launch) are all contiguous.
+    // records (8 or 16 bytes each, scattered to the slot by the index-ordered form: 21 % of that launch at 16) are all contiguous.
     const size_t dst = slot_of != nullptr ? (size_t)slot_of[i] : (size_t)i;
     if (sh_by_slot != nullptr && blockIdx.y == 0)
         for (int k = 0; k < sh_floats; ++k) sh_by_slot[dst * sh_floats + k] = sh[(size_t)i * sh_floats + k];
@@ -140,20 +144,44 @@ __device__ __forceinline__ TileRect tight_rect(TileRect r, float px, float py, f
     return t;
 }
 
+// Bin record of a (frame, Gaussian): the final tile rect and the depth bits.  An empty rect is all-zero coordinates.
+//   BinRec16 = uint4 {x0 | y0 << 16, x1 | y1 << 16, depth bits, 0}                any grid
+//   BinRec8  = uint2 {x0 | y0 << 8 | x1 << 16 | y1 << 24, depth bits}             gx, gy <= BIN_REC8_MAX_GRID (coordinates lie in [0, gx], [0, gy])
+typedef uint4 BinRec16;
+typedef uint2 BinRec8;
+template <typename REC> __device__ __forceinline__ REC binrec_pack(TileRect r, uint32_t depth_bits);
+template <> __device__ __forceinline__ BinRec16 binrec_pack<BinRec16>(TileRect r, uint32_t depth_bits) {
+    return make_uint4((uint32_t)r.x0 | ((uint32_t)r.y0 << 16), (uint32_t)r.x1 | ((uint32_t)r.y1 << 16), depth_bits, 0u);
+}
+template <> __device__ __forceinline__ BinRec8 binrec_pack<BinRec8>(TileRect r, uint32_t depth_bits) {
+    return make_uint2((uint32_t)r.x0 | ((uint32_t)r.y0 << 8) | ((uint32_t)r.x1 << 16) | ((uint32_t)r.y1 << 24), depth_bits);
+}
+__device__ __forceinline__ TileRect binrec_rect16(uint32_t w0, uint32_t w1) {
+    return TileRect{(int)(w0 & 0xffffu), (int)(w0 >> 16), (int)(w1 & 0xffffu), (int)(w1 >> 16)};
+}
+__device__ __forceinline__ TileRect binrec_rect8(uint32_t w) {
+    return TileRect{(int)(w & 0xffu), (int)((w >> 8) & 0xffu), (int)((w >> 16) & 0xffu), (int)(w >> 24)};
+}
+__device__ __forceinline__ TileRect binrec_rect(const BinRec16& b) { return binrec_rect16(b.x, b.y); }
+__device__ __forceinline__ TileRect binrec_rect(const BinRec8& b) { return binrec_rect8(b.x); }
+__device__ __forceinline__ uint32_t binrec_depth(const BinRec16& b) { return b.z; }
+__device__ __forceinline__ uint32_t binrec_depth(const BinRec8& b) { return b.y; }
+
 // SHARED: a0 = the stage-A records [slices][P][4 x float4] (see activate_cov_kernel), frames[f].reserved[0] = the frame's slice
 // WAVE_FRAMES (bucket binning without shared activation; block_sums and tiles_touched are null by construction): the workgroup owns 64
 // consecutive Gaussians instead of 256 and its four waves walk different frames -- wave w takes frames 4 G by + w + 4 ff, ff = 0 .. G - 1
 // (G = PRE_WAVE_FB) -- so the SH rows are staged once per 4 G frames and the raw inputs come across the fabric once per 4 G frames, on a grid
 // that keeps ceil(P / 64) x ceil(F / 4G) workgroups.  One barrier, after the staging; the waves never meet again.  What a wave loads and stores
 // per frame (delta rows, quad-transposed splat records, bin records) and the per-Gaussian arithmetic are those of the other mapping.
-template <bool SHARED, bool WAVE_FRAMES = false>
+// REC: the bin-record form (binrec points at [F*P] of them).
+template <bool SHARED, bool WAVE_FRAMES = false, typename REC = BinRec16>
 __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
     PreParams pp, const GvfRastFrame* __restrict__ frames, const float* __restrict__ a0,
     const float* __restrict__ a1, const float* __restrict__ a2, const float* __restrict__ a3,
     const float* __restrict__ sh, const float* __restrict__ colors_precomp,
     const float* __restrict__ cov3D_precomp, const float* __restrict__ delta, float4* __restrict__ splats,
     uint32_t* __restrict__ tiles_touched,
-    int32_t* __restrict__ radii, uint32_t* __restrict__ block_sums, uint4* __restrict__ binrec,
+    int32_t* __restrict__ radii, uint32_t* __restrict__ block_sums, REC* __restrict__ binrec,
     const uint32_t* __restrict__ bin_slot /* Gaussian -> position of its bin record inside a frame; null = identity */) {
     static_assert(!(SHARED && WAVE_FRAMES), "the shared-activation launch keeps the 256-Gaussian mapping");
     extern __shared__ __attribute__((aligned(16))) float sh_lds[];  // [PRE_GPB][M*3] + 4 wave sums
@@ -339,11 +367,9 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(
             const uint32_t* gid_of = SHARED ? reinterpret_cast<const uint32_t*>(a1) : nullptr;
             radii[gid_of != nullptr ? (size_t)f * P + gid_of[i] : o] = radius_out;
         }
-        // bucket binning: the final tile rect and the depth, 16 B that the count / scatter passes gather by id
-        if (binrec != nullptr) {
-            binrec[(size_t)f * P + my_slot] = make_uint4((uint32_t)rect.x0 | ((uint32_t)rect.y0 << 16),
-                                                         (uint32_t)rect.x1 | ((uint32_t)rect.y1 << 16), __float_as_uint(gC.y), 0u);
-        }
+        // bucket binning: the final tile rect and the depth, 8 or 16 B that the count / scatter passes read (one store per lane: whole
+        // lines per wave in index and slot order)
+        if (binrec != nullptr) binrec[(size_t)f * P + my_slot] = binrec_pack<REC>(rect, __float_as_uint(gC.y));
     }
 
     // Quad-transposed record store: lane 4 g + j writes piece j (16 bytes; piece 3 = the padding) of the records of lanes
@@ -554,11 +580,11 @@ __global__ void frame_counts_kernel(const uint32_t* __restrict__ frame_base, int
 // scatter pass: cursor allocation, the base is left in the table and an LDS counter hands out the slots).  A block
 // whose window exceeds WIN_MAX tiles (incoherent order) pays one global atomic per instance instead.
 // rec_by_id = 0: the records sit at their slots (preprocess_kernel's bin_slot) and are read as one stream; 1: they sit at the Gaussian's index
-// and are gathered, and xcd_frames = 1 then lays the grid out 1-D so that each XCD takes whole frames (see the host).
+// and are gathered, and xcd_frames = 1 then lays the grid out 1-D so that each XCD takes whole frames (see the host).  REC: the record form.
 constexpr int WIN_MAX = 2048;
 
-template <bool SCATTER>
-__global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy, const uint4* __restrict__ binrec,
+template <bool SCATTER, typename REC>
+__global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy, const REC* __restrict__ binrec,
                                                           const uint32_t* __restrict__ order,
                                                           uint32_t* __restrict__ tile_count /* count pass */,
                                                           uint32_t* __restrict__ cursor /* scatter pass */,
@@ -594,10 +620,10 @@ __global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy,
         x0[k] = y0[k] = x1[k] = y1[k] = 0; key[k] = 0;
         if (s < P) {
             const uint32_t id = order != nullptr ? order[s] : (uint32_t)s;
-            const uint4 br = binrec[(size_t)f * P + (rec_by_id ? id : (uint32_t)s)];
-            x0[k] = (int)(br.x & 0xffffu); y0[k] = (int)(br.x >> 16);
-            x1[k] = (int)(br.y & 0xffffu); y1[k] = (int)(br.y >> 16);
-            key[k] = ((uint64_t)br.z << 32) | id;                      // depth bits above the Gaussian id
+            const REC br = binrec[(size_t)f * P + (rec_by_id ? id : (uint32_t)s)];
+            const TileRect r = binrec_rect(br);
+            x0[k] = r.x0; y0[k] = r.y0; x1[k] = r.x1; y1[k] = r.y1;
+            key[k] = ((uint64_t)binrec_depth(br) << 32) | id;          // depth bits above the Gaussian id
             if (x1[k] > x0[k] && y1[k] > y0[k]) {
                 bx0 = min(bx0, x0[k]); by0 = min(by0, y0[k]); bx1 = max(bx1, x1[k]); by1 = max(by1, y1[k]);
             } else {
@@ -662,9 +688,20 @@ __global__ __launch_bounds__(PRE_THREADS) void bin_kernel(int P, int gx, int gy,
 // fit the table (ntiles <= BINX_TAB).  cursor, total, payload, frame_base and num_rendered are read by no code; they keep the
 // kernel's arguments as they were when it also had a scatter form.
 constexpr int BINX_THREADS = 512;
-constexpr int BINX_SPT = 4;                          // records in flight per thread
+constexpr int BINX_SPT = 4;                          // 16-byte loads in flight per thread
 
-__global__ __launch_bounds__(BINX_THREADS) void bin_index_kernel(int P, int gx, const uint4* __restrict__ binrec,
+// the instances of one rect into the workgroup's tile table
+__device__ __forceinline__ void binx_count(uint32_t* s_tab, int gx, TileRect r) {
+    for (int y = r.y0; y < r.y1; ++y)
+        for (int x = r.x0; x < r.x1; ++x) atomicAdd(&s_tab[y * gx + x], 1u);
+}
+
+// REC: the record form.  Either form keeps BINX_SPT 16-byte loads in flight per thread; a load brings one 16-byte record or two 8-byte
+// ones.  The pairs of the 8-byte form are taken at even positions of the whole [F*P] array (frame f starts at record f P, which may be
+// odd), so every load is 16-byte aligned; a pair's record outside the workgroup's own range [a0, a1) is dropped.  The last pair of the
+// array may reach one record past F P: the array has room for 16 bytes per record (carve).
+template <typename REC>
+__global__ __launch_bounds__(BINX_THREADS) void bin_index_kernel(int P, int gx, const REC* __restrict__ binrec,
                                                                  uint32_t* __restrict__ tile_count,
                                                                  uint32_t* __restrict__ cursor,
                                                                  const uint32_t* __restrict__ total,
@@ -673,22 +710,36 @@ __global__ __launch_bounds__(BINX_THREADS) void bin_index_kernel(int P, int gx, 
     __shared__ uint32_t s_tab[BINX_TAB];
     const int t = threadIdx.x, f = blockIdx.y;
     const int g0 = (int)blockIdx.x * BINX_PER_WG, g1 = min(P, g0 + BINX_PER_WG);
-    const uint4* rec = binrec + (size_t)f * P;
     for (int e = t; e < ntiles; e += BINX_THREADS) s_tab[e] = 0u;
     __syncthreads();
-    for (int base = g0; base < g1; base += BINX_SPT * BINX_THREADS) {
-        uint4 br[BINX_SPT];
+    if constexpr (sizeof(REC) == 16) {
+        const uint4* rec = binrec + (size_t)f * P;
+        for (int base = g0; base < g1; base += BINX_SPT * BINX_THREADS) {
+            uint4 br[BINX_SPT];
 #pragma unroll
-        for (int k = 0; k < BINX_SPT; ++k) {
-            const int s = base + k * BINX_THREADS + t;
-            br[k] = s < g1 ? rec[s] : make_uint4(0u, 0u, 0u, 0u);     // {0, 0, 0, 0}: an empty rect
+            for (int k = 0; k < BINX_SPT; ++k) {
+                const int s = base + k * BINX_THREADS + t;
+                br[k] = s < g1 ? rec[s] : make_uint4(0u, 0u, 0u, 0u);     // {0, 0, 0, 0}: an empty rect
+            }
+#pragma unroll
+            for (int k = 0; k < BINX_SPT; ++k) binx_count(s_tab, gx, binrec_rect16(br[k].x, br[k].y));
         }
+    } else {
+        const size_t a0 = (size_t)f * P + g0, a1 = (size_t)f * P + g1;   // this workgroup's records, as positions in the whole array
+        const uint4* pairs = reinterpret_cast<const uint4*>(binrec);       // pair j = records 2 j, 2 j + 1
+        for (size_t jbase = a0 >> 1; 2 * jbase < a1; jbase += BINX_SPT * BINX_THREADS) {
+            uint4 br[BINX_SPT];
 #pragma unroll
-        for (int k = 0; k < BINX_SPT; ++k) {
-            const int x0 = (int)(br[k].x & 0xffffu), y0 = (int)(br[k].x >> 16);
-            const int x1 = (int)(br[k].y & 0xffffu), y1 = (int)(br[k].y >> 16);
-            for (int y = y0; y < y1; ++y)
-                for (int x = x0; x < x1; ++x) atomicAdd(&s_tab[y * gx + x], 1u);
+            for (int k = 0; k < BINX_SPT; ++k) {
+                const size_t j = jbase + k * BINX_THREADS + t;
+                br[k] = 2 * j < a1 ? pairs[j] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (int k = 0; k < BINX_SPT; ++k) {
+                const size_t a = 2 * (jbase + k * BINX_THREADS + t);
+                binx_count(s_tab, gx, binrec_rect8(a >= a0 ? br[k].x : 0u));       // (a < a1, or the pair is zero)
+                binx_count(s_tab, gx, binrec_rect8(a + 1 < a1 ? br[k].z : 0u));    // (a + 1 >= a0 always)
+            }
         }
     }
     __syncthreads();
@@ -869,9 +920,34 @@ template <bool SHARED, bool WAVE_FRAMES = false>
 void launch_preprocess(hipStream_t stream, const RastPlan& plan, const PreParams& pp, const Workspace& w, const PreArgs& a) {
     const int32_t* g = WAVE_FRAMES ? plan.wf_grid : plan.pre_grid;
     const size_t lds = (size_t)(WAVE_FRAMES ? plan.wf_lds_bytes : plan.pre_lds_bytes);
-    hipLaunchKernelGGL((preprocess_kernel<SHARED, WAVE_FRAMES>), dim3(g[0], g[1]), dim3(PRE_THREADS), lds, stream, pp, w.frames, a.a0, a.a1,
-                       a.a2, a.a3, a.sh, a.colors_precomp, a.cov3D_precomp, a.delta, w.splats, a.tiles_touched, a.radii, a.block_sums,
-                       a.binrec, a.bin_slot);
+    if (plan.rec8)
+        hipLaunchKernelGGL((preprocess_kernel<SHARED, WAVE_FRAMES, BinRec8>), dim3(g[0], g[1]), dim3(PRE_THREADS), lds, stream, pp, w.frames,
+                           a.a0, a.a1, a.a2, a.a3, a.sh, a.colors_precomp, a.cov3D_precomp, a.delta, w.splats, a.tiles_touched, a.radii,
+                           a.block_sums, reinterpret_cast<BinRec8*>(a.binrec), a.bin_slot);
+    else
+        hipLaunchKernelGGL((preprocess_kernel<SHARED, WAVE_FRAMES, BinRec16>), dim3(g[0], g[1]), dim3(PRE_THREADS), lds, stream, pp, w.frames,
+                           a.a0, a.a1, a.a2, a.a3, a.sh, a.colors_precomp, a.cov3D_precomp, a.delta, w.splats, a.tiles_touched, a.radii,
+                           a.block_sums, a.binrec, a.bin_slot);
+}
+
+// The count pass (index order, or bin_kernel<false> over the Morton slots) and the scatter pass over records of form REC
+template <typename REC>
+void launch_bin_count(hipStream_t stream, const RastCall& c, const RastPlan& plan, const Workspace& w, const uint32_t* order) {
+    const REC* rec = reinterpret_cast<const REC*>(w.binrec);
+    const int gather = plan.rec_gather ? 1 : 0;
+    if (plan.index_count)
+        hipLaunchKernelGGL((bin_index_kernel<REC>), dim3(plan.binx_grid[0], plan.binx_grid[1]), dim3(BINX_THREADS), 0, stream, c.P, plan.gx, rec,
+                           w.tile_count, w.cursor, w.total, w.keys, plan.ntiles, nullptr, nullptr);
+    else
+        hipLaunchKernelGGL((bin_kernel<false, REC>), dim3(plan.bin_grid[0], plan.bin_grid[1]), dim3(PRE_THREADS), 0, stream, c.P, plan.gx, plan.gy,
+                           rec, order, w.tile_count, w.cursor, w.total, w.keys, nullptr, nullptr, gather, gather, c.F);
+}
+template <typename REC>
+void launch_bin_scatter(hipStream_t stream, const RastCall& c, const RastPlan& plan, const Workspace& w, const uint32_t* order) {
+    const int gather = plan.rec_gather ? 1 : 0;
+    hipLaunchKernelGGL((bin_kernel<true, REC>), dim3(plan.bin_grid[0], plan.bin_grid[1]), dim3(PRE_THREADS), 0, stream, c.P, plan.gx, plan.gy,
+                       reinterpret_cast<const REC*>(w.binrec), order, w.tile_count, w.cursor, w.total, w.keys, w.frame_base,
+                       c.out_num_rendered, gather, gather, c.F);
 }
 
 // The call's own inputs, as both fused launches (wave-frames or not) and the radix path read them
@@ -977,15 +1053,9 @@ int gvf_rast::front_end_bucket(hipStream_t stream, const RastCall& c, const Rast
     }
     // bin passes (bin_kernel): Morton order over records at their slots (shared activation) or gathered from the Gaussians' indices, the
     // gather with a 1-D grid in which each XCD takes whole frames.  The count pass only sums per segment, so it may walk the records in
-    // index order instead (bin_index_kernel).
-    const dim3 bin_grid(plan.bin_grid[0], plan.bin_grid[1]);
-    const int gather = plan.rec_gather ? 1 : 0;
-    if (plan.index_count)
-        hipLaunchKernelGGL(bin_index_kernel, dim3(plan.binx_grid[0], plan.binx_grid[1]), dim3(BINX_THREADS), 0, stream, P, plan.gx, w.binrec,
-                           w.tile_count, w.cursor, w.total, w.keys, plan.ntiles, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL(bin_kernel<false>, bin_grid, dim3(PRE_THREADS), 0, stream, P, plan.gx, plan.gy, w.binrec, order,
-                           w.tile_count, w.cursor, w.total, w.keys, nullptr, nullptr, gather, gather, F);
+    // index order instead (bin_index_kernel).  Both passes read the record form the projection launch stored (plan.rec8).
+    if (plan.rec8) launch_bin_count<BinRec8>(stream, c, plan, w, order);
+    else launch_bin_count<BinRec16>(stream, c, plan, w, order);
     GVF_CHECK_LAUNCH();
     prof_mark(stream, marks, 2);
     hipLaunchKernelGGL(seg_sums_kernel, dim3(plan.scan_blocks), dim3(1024), 0, stream, w.tile_count, plan.nseg, w.partial);
@@ -997,8 +1067,8 @@ int gvf_rast::front_end_bucket(hipStream_t stream, const RastCall& c, const Rast
     GVF_CHECK_LAUNCH();
     prof_mark(stream, marks, 3);
     if (c.max_rendered > 0) {
-        hipLaunchKernelGGL(bin_kernel<true>, bin_grid, dim3(PRE_THREADS), 0, stream, P, plan.gx, plan.gy, w.binrec, order,
-                           w.tile_count, w.cursor, w.total, w.keys, w.frame_base, c.out_num_rendered, gather, gather, F);
+        if (plan.rec8) launch_bin_scatter<BinRec8>(stream, c, plan, w, order);
+        else launch_bin_scatter<BinRec16>(stream, c, plan, w, order);
         GVF_CHECK_LAUNCH();
     }
     if (c.out_radii != nullptr &&

@@ -34,6 +34,7 @@ constexpr int BIN_SPT = 4;               // bin_kernel: slots per thread
 constexpr int BIN_SLOTS = PRE_THREADS * BIN_SPT;
 constexpr int BINX_TAB = 4096;           // bin_index_kernel: tiles of its whole-frame LDS table
 constexpr int BINX_PER_WG = 8192;        //                   Gaussians per workgroup
+constexpr int BIN_REC8_MAX_GRID = 255;   // 8-byte bin records: a rect coordinate lies in [0, gx] or [0, gy] and gets 8 bits
 constexpr int MORTON_BINS = 1 << 15;
 constexpr int ORDER_TILES_MIN_SEGS = 2048;   // heaviest-tiles-first blend: worth a launch when the frames' workgroups outnumber the chip's resident slots
 
@@ -89,6 +90,7 @@ struct RastSwitches {
     bool slot_order = true;          // GVF_RAST_SLOT_ORDER
     bool pre_wave_frames = true;     // GVF_RAST_PRE_WAVE_FRAMES
     bool blend_order = true;         // GVF_RAST_BLEND_ORDER
+    bool bin_rec8 = true;            // GVF_RAST_BIN_REC8
 };
 
 // What of a call's arguments the plan depends on (pointers only as present / absent)
@@ -98,10 +100,12 @@ struct PlanInputs {
     int64_t max_rendered;
 };
 
-// The public part (flags, sizes, grids, LDS bytes: include/gvf_rast.h) + the slice table the front end and the upload launch need.
+// The public part (flags, sizes, grids, LDS bytes: include/gvf_rast.h) + the slice table the front end and the upload launch need and the
+// bin-record form (gvf_rast_bin_record_bytes shows it to the tests).
 struct RastPlan : GvfRastPlan {
     int32_t di[ACT_MAX_SLICES];            // delta index of each slice (shared activation)
     std::vector<int32_t> frame_slice;      // [F]: the frame's slice; all zero unless `shared` (goes to the device copy's reserved[0])
+    bool rec8;                             // bin records in the 8-byte form (BinRec8, rast_common.h) instead of the 16-byte one
 };
 
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -143,6 +147,9 @@ inline RastPlan plan_call(const GvfRastSettings& st, const GvfRastFrame* frames_
     // preprocess_kernel<false> stores the bin records at the Gaussians' indices, bin_kernel gathers them in Morton order
     p.rec_gather = p.bucket && !p.shared && p.morton;
     p.wave_frames = !p.shared && p.bucket && sw.pre_wave_frames;
+    // 8-byte bin records (half the bytes through preprocess's stores and both bin passes; a frame's records then fit one XCD's L2 in the
+    // gather): every coordinate of a tile rect must fit 8 bits.  Larger grids (images beyond 4080 px) keep the 16-byte form.
+    p.rec8 = p.bucket && sw.bin_rec8 && p.gx <= BIN_REC8_MAX_GRID && p.gy <= BIN_REC8_MAX_GRID;
     p.order_tiles = sw.blend_order && P > 0 && p.nb > 0 && in.max_rendered > 0 && (size_t)F * p.ntiles >= (size_t)ORDER_TILES_MIN_SEGS;
 
     p.pre_grid[0] = p.nb; p.pre_grid[1] = ceil_div(F, PRE_FB);

@@ -439,6 +439,14 @@ def call_plan(settings, frames, P, M, max_rendered, fused=True, has_sh=True, has
     return out
 
 
+def bin_record_bytes(settings):
+    """Size of the bin records a forward call with these settings keeps (gvf_rast_bin_record_bytes): 8 when the tile grid is at most
+    255 x 255 under bucket binning and GVF_RAST_BIN_REC8 is not "0", else 16.  Host only, a test aid."""
+    out = ctypes.c_int(0)
+    _lib.check(_lib.lib().gvf_rast_bin_record_bytes(ctypes.byref(settings), ctypes.byref(out)), "gvf_rast_bin_record_bytes")
+    return int(out.value)
+
+
 def gaussian_activate(act, xyz_raw, features_dc, scaling_raw, rotation_raw, opacity_raw, delta=None):
     """GaussianModel.get_*_with_delta on the device (csrc/rast_front.hip activate_kernel)."""
     _lib.require_cuda(xyz_raw)

@@ -279,6 +279,13 @@ int gvf_rast_call_plan(const GvfRastSettings* settings_host, const GvfRastFrame*
                        int has_sh, int has_colors_precomp, int has_cov3D_precomp, int has_delta, int has_subpixel_offset,
                        int64_t max_rendered, GvfRastPlan* out);
 
+/* Diagnostic of the bin-record form (a private decision of the same plan): the bucket binning keeps per (frame, Gaussian) the final tile
+ * rect and the depth bits, in 8 bytes {x0 | y0 << 8 | x1 << 16 | y1 << 24, depth bits} when the tile grid is at most 255 x 255 (gx, gy <=
+ * 255: images up to 4080 px either way), else in 16 bytes {x0 | y0 << 16, x1 | y1 << 16, depth bits, 0}.  Both are lossless: frames, alpha,
+ * depth, radii and num_rendered are the same bits.  GVF_RAST_BIN_REC8=0 in the environment (read per call) forces the 16-byte form.
+ * Writes 8 or 16 to *bytes (16 for radix binning, which keeps no bin records).  Runs no launch. */
+int gvf_rast_bin_record_bytes(const GvfRastSettings* settings_host, int* bytes);
+
 /* Diagnostic of the frames' grouping by delta slice, which the forward's plan and the batched backward share: writes the table the
  * backward uploads -- [F] frame indices grouped by slice (slices in order of first use, frames ascending inside one) | [n + 1] group
  * starts | [n] the slices' delta indices (-1: no delta) -- to table_host (room for 3 F + 1 words) and n to *n_slices.  max_slices > 0:
