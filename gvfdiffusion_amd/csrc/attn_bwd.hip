@@ -23,6 +23,10 @@
 // Determinism: every gradient element is summed by one wave in tile order; no atomics, no workgroup waits on another.
 // Short sequences (Lq, Lk <= 32, head_dim 32: the DiT's temporal attention): one wave per (sequence, head) problem, everything in
 // registers and a per-wave LDS slab, no workspace.
+// Ragged form (gvf_attn_varlen_bwd: packed [T, H, C] tensors, device cu_seqlens, the sparse seam sparse/attention/full_attn.py): the same
+// three kernels, instantiated with VARLEN.  Only the problem decode differs (problem_of): a workgroup reads its sequence's row base and
+// lengths from cu_seqlens, the grids are sized from the longest lengths, and a workgroup whose owned block lies past its sequence
+// leaves before the first barrier.  No length crosses to the host; the split rule sees the host-known arguments only.
 #include <cstdlib>
 #include "gvf_common.h"
 #include "gvf_lp.h"
@@ -45,7 +49,9 @@ struct BwdParams {
     unsigned short *dq, *dk, *dv;
     float *lse2, *delta;
     float* part;                     // key sweep split over the queries: fp32 partial dK, dV [2][n_split][N H][Lk][D]
-    int n_outer, n_inner, Lq, Lk, H, x_blocks, n_split;
+    int n_outer, n_inner, Lq, Lk, H, x_blocks, n_split;    // ragged: n_outer sequences, n_inner 1, Lq / Lk the longest (they size the grids)
+    const int32_t *cu_q, *cu_k;      // ragged: sequence `outer` owns token rows [cu[outer], cu[outer + 1]) of the packed tensors
+    long long total_q, total_k;      // ragged: rows of the packed tensors; statistics are [H][total_q], partials [2][n_split][H][total_k][D]
     long long q_s[4], k_s[4], v_s[4], o_s[4], do_s[4], dq_s[4], dk_s[4], dv_s[4];     // {outer, inner, seq, head} in elements
     float scale, scale_log2e, inv_scale_log2e;
 };
@@ -79,6 +85,31 @@ __device__ __forceinline__ void decode_block(const BwdParams& p, int& xb, int& h
     prob = ((long long)outer * p.n_inner + inner) * p.H + head;
 }
 
+// Where a workgroup gets its problem from.  Dense: the call's lengths, rows from the tensors' bases, statistics (N, H, Lq).  Ragged: the
+// row bases and lengths of sequence `outer` are read from cu_seqlens once per workgroup (uniform), statistics and partials are indexed
+// [head][packed row].  stat0 / part0: first statistics row of the problem / first partial row of one split chunk.
+struct Problem {
+    int Lq, Lk;
+    long long q0, k0, stat0, part0, part_rows;
+};
+template <bool VARLEN>
+__device__ __forceinline__ Problem problem_of(const BwdParams& p, int outer, int head, long long prob) {
+    Problem w;
+    if (VARLEN) {
+        w.q0 = p.cu_q[outer]; w.Lq = p.cu_q[outer + 1] - (int)w.q0;
+        w.k0 = p.cu_k[outer]; w.Lk = p.cu_k[outer + 1] - (int)w.k0;
+        w.stat0 = (long long)head * p.total_q + w.q0;
+        w.part0 = (long long)head * p.total_k + w.k0;
+        w.part_rows = (long long)p.H * p.total_k;
+    } else {
+        w.q0 = 0; w.k0 = 0; w.Lq = p.Lq; w.Lk = p.Lk;
+        w.stat0 = prob * p.Lq;
+        w.part0 = prob * p.Lk;
+        w.part_rows = (long long)p.n_outer * p.n_inner * p.H * p.Lk;
+    }
+    return w;
+}
+
 __device__ __forceinline__ uint4 ld16(const unsigned short* ptr, bool ok) {
     return ok ? *reinterpret_cast<const uint4*>(ptr) : make_uint4(0u, 0u, 0u, 0u);
 }
@@ -104,7 +135,7 @@ __device__ __forceinline__ void store4(unsigned short* dst, const f32x16& acc, i
 // ---------------------------------------------------------------------------------------------------------------------
 // Row statistics: one workgroup = 128 queries of one (sequence, head), a wave 32; the keys stream through LDS in 32-row tiles.
 // S^T = K Q^T (query on the lane), online maximum / sum in the log2 domain.
-template <int D, int DT>
+template <int D, int DT, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
     using C = Cfg<D>;
     typedef GvfLp<DT> LP;
@@ -115,13 +146,16 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
     int xb, head, inner, outer, sp;
     long long prob;
     decode_block(p, xb, head, inner, outer, prob, sp);
-    const unsigned short* qp = p.q + head_off(p.q_s, outer, inner, head);
-    const unsigned short* kp = p.k + head_off(p.k_s, outer, inner, head);
-    const unsigned short* op = p.o + head_off(p.o_s, outer, inner, head);
-    const unsigned short* gp = p.dout + head_off(p.do_s, outer, inner, head);
+    const Problem w = problem_of<VARLEN>(p, outer, head, prob);
+    const int Lq = w.Lq, Lk = w.Lk;
+    if (VARLEN && (xb * XB >= Lq || Lk <= 0)) return;      // whole workgroup (uniform): no such query block, or no key to attend to
+    const unsigned short* qp = p.q + head_off(p.q_s, outer, inner, head) + w.q0 * p.q_s[2];
+    const unsigned short* kp = p.k + head_off(p.k_s, outer, inner, head) + w.k0 * p.k_s[2];
+    const unsigned short* op = p.o + head_off(p.o_s, outer, inner, head) + w.q0 * p.o_s[2];
+    const unsigned short* gp = p.dout + head_off(p.do_s, outer, inner, head) + w.q0 * p.do_s[2];
 
     const int qrow = xb * XB + wave * 32 + l31;
-    const bool qvalid = qrow < p.Lq;
+    const bool qvalid = qrow < Lq;
     x8 qf[C::NS];
     float delta = 0.f;
 #pragma unroll
@@ -132,11 +166,11 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
     }
     delta += __shfl_xor(delta, 32, 64);
 
-    const int n_tiles = (p.Lk + YT - 1) / YT;
+    const int n_tiles = (Lk + YT - 1) / YT;
     const bool stager = tid < YT * C::KC;
     const int st_row = tid / C::KC, st_c = tid % C::KC;
     const int st_slot = st_row * C::KC + (st_c ^ C::swz(st_row));
-    uint4 kreg = ld16(kp + (long long)st_row * p.k_s[2] + st_c * 8, stager && st_row < p.Lk);
+    uint4 kreg = ld16(kp + (long long)st_row * p.k_s[2] + st_c * 8, stager && st_row < Lk);
     if (stager) sK[0][st_slot] = kreg;
     __syncthreads();
 
@@ -145,7 +179,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
         const int buf = t & 1;
         if (t + 1 < n_tiles) {
             const int y = (t + 1) * YT + st_row;
-            kreg = ld16(kp + (long long)y * p.k_s[2] + st_c * 8, stager && y < p.Lk);
+            kreg = ld16(kp + (long long)y * p.k_s[2] + st_c * 8, stager && y < Lk);
         }
         f32x16 s_acc;
 #pragma unroll
@@ -156,10 +190,10 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
             s_acc = LP::mfma32(kf, qf[st], s_acc);
         }
         const int key0 = t * YT;
-        if (key0 + YT > p.Lk) {                     // last, partial tile (uniform): keys past Lk leave the softmax
+        if (key0 + YT > Lk) {                     // last, partial tile (uniform): keys past Lk leave the softmax
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                if (key0 + crow(r, half) >= p.Lk) s_acc[r] = -INFINITY;
+                if (key0 + crow(r, half) >= Lk) s_acc[r] = -INFINITY;
         }
         float mloc = s_acc[0];
 #pragma unroll
@@ -177,14 +211,14 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_stats_kernel(BwdParams p) {
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     if (qvalid && half == 0) {
-        p.lse2[prob * p.Lq + qrow] = m_run + log2f(l_tot);
-        p.delta[prob * p.Lq + qrow] = delta;
+        p.lse2[w.stat0 + qrow] = m_run + log2f(l_tot);
+        p.delta[w.stat0 + qrow] = delta;
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The gradient sweeps.  KEYOWN: the workgroup owns keys and streams queries (dK, dV); otherwise it owns queries and streams keys (dQ).
-template <int D, bool KEYOWN, int DT>
+template <int D, bool KEYOWN, int DT, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
     using C = Cfg<D>;
     typedef GvfLp<DT> LP;
@@ -198,19 +232,23 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
     int xb, head, inner, outer, sp;
     long long prob;
     decode_block(p, xb, head, inner, outer, prob, sp);
-    const int Lx = KEYOWN ? p.Lk : p.Lq, Ly = KEYOWN ? p.Lq : p.Lk;
-    const unsigned short* qp = p.q + head_off(p.q_s, outer, inner, head);
-    const unsigned short* kp = p.k + head_off(p.k_s, outer, inner, head);
-    const unsigned short* vp = p.v + head_off(p.v_s, outer, inner, head);
-    const unsigned short* gp = p.dout + head_off(p.do_s, outer, inner, head);
+    const Problem w = problem_of<VARLEN>(p, outer, head, prob);
+    const int Lx = KEYOWN ? w.Lk : w.Lq, Ly = KEYOWN ? w.Lq : w.Lk;
+    // ragged: an owned block past its sequence's length has nothing to do (whole workgroup, uniform).  A sequence with no streamed rows
+    // (keys without queries, queries without keys) runs no tile below and stores its zero accumulators: those gradient rows are +0.
+    if (VARLEN && xb * XB >= Lx) return;
+    const unsigned short* qp = p.q + head_off(p.q_s, outer, inner, head) + w.q0 * p.q_s[2];
+    const unsigned short* kp = p.k + head_off(p.k_s, outer, inner, head) + w.k0 * p.k_s[2];
+    const unsigned short* vp = p.v + head_off(p.v_s, outer, inner, head) + w.k0 * p.v_s[2];
+    const unsigned short* gp = p.dout + head_off(p.do_s, outer, inner, head) + w.q0 * p.do_s[2];
     const unsigned short* x1p = KEYOWN ? kp : qp;
     const unsigned short* x2p = KEYOWN ? vp : gp;
     const unsigned short* y1p = KEYOWN ? qp : kp;
     const unsigned short* y2p = KEYOWN ? gp : vp;
     const long long x1_sl = KEYOWN ? p.k_s[2] : p.q_s[2], x2_sl = KEYOWN ? p.v_s[2] : p.do_s[2];
     const long long y1_sl = KEYOWN ? p.q_s[2] : p.k_s[2], y2_sl = KEYOWN ? p.do_s[2] : p.v_s[2];
-    const float* lse2 = p.lse2 + prob * p.Lq;
-    const float* delta = p.delta + prob * p.Lq;
+    const float* lse2 = p.lse2 + w.stat0;
+    const float* delta = p.delta + w.stat0;
 
     // ---- owned rows: B operands.  Lane (x = lane & 31, half): X[x][16 s + 8 half .. + 7]
     const int xrow = xb * XB + wave * 32 + l31;
@@ -223,7 +261,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
         x2f[s] = __builtin_bit_cast(x8, ld16(x2p + (long long)xrow * x2_sl + 16 * s + 8 * half, xvalid));
     }
     float nl_lane = 0.f, nd_lane = 0.f;                                    // sweep Q: the lane's query constants
-    if (!KEYOWN && xvalid) {
+    if (!KEYOWN && xvalid && (!VARLEN || Ly > 0)) {                       // (no keys: no statistics were written, none are used)
         nl_lane = -lse2[xrow] * p.inv_scale_log2e;
         nd_lane = -delta[xrow];
     }
@@ -245,6 +283,7 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
         st_c[i] = w % C::KC;
     }
     // streamed tiles [t0, t1) of this workgroup: all of them, or chunk `sp` of n_split when the key sweep is split over the queries
+    // (ragged: chunks of the sequence's own tiles; a chunk past them runs no tile and hands zeros to the reduction)
     const int n_tiles_all = (Ly + YT - 1) / YT;
     const int tiles_per = (n_tiles_all + p.n_split - 1) / p.n_split;
     const int t0 = sp * tiles_per, t1 = min(n_tiles_all, t0 + tiles_per);
@@ -347,9 +386,8 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
     // ---- epilogue: accumulator column = owned row, register r = d (r & 3) + 8 (r >> 2) + 4 half (+ 32 dt)
     if (KEYOWN && p.n_split > 1) {                   // split key sweep: fp32 partials, summed in chunk order by attn_bwd_reduce_kernel
         if (xvalid) {
-            const long long n_prob = (long long)p.n_outer * p.n_inner * p.H;
-            float* d1 = p.part + (((long long)sp * n_prob + prob) * p.Lk + xrow) * D;
-            float* d2 = d1 + (long long)p.n_split * n_prob * p.Lk * D;
+            float* d1 = p.part + ((long long)sp * w.part_rows + w.part0 + xrow) * D;
+            float* d2 = d1 + (long long)p.n_split * w.part_rows * D;
 #pragma unroll
             for (int dt = 0; dt < C::ND; ++dt)
 #pragma unroll
@@ -362,14 +400,14 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
         return;
     }
     if (xvalid) {
-        unsigned short* g1 = KEYOWN ? p.dk + head_off(p.dk_s, outer, inner, head) + (long long)xrow * p.dk_s[2]
-                                    : p.dq + head_off(p.dq_s, outer, inner, head) + (long long)xrow * p.dq_s[2];
+        unsigned short* g1 = KEYOWN ? p.dk + head_off(p.dk_s, outer, inner, head) + (w.k0 + xrow) * p.dk_s[2]
+                                    : p.dq + head_off(p.dq_s, outer, inner, head) + (w.q0 + xrow) * p.dq_s[2];
 #pragma unroll
         for (int dt = 0; dt < C::ND; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) store4<DT>(g1 + dt * 32 + 8 * g + 4 * half, acc1[dt], g);
         if (KEYOWN) {
-            unsigned short* g2 = p.dv + head_off(p.dv_s, outer, inner, head) + (long long)xrow * p.dv_s[2];
+            unsigned short* g2 = p.dv + head_off(p.dv_s, outer, inner, head) + (w.k0 + xrow) * p.dv_s[2];
 #pragma unroll
             for (int dt = 0; dt < C::ND; ++dt)
 #pragma unroll
@@ -379,19 +417,22 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_sweep_kernel(BwdParams p) {
 }
 
 // dK, dV = the sum of the split key sweep's fp32 partials in chunk order, rounded once.  One thread per four channels of a key row.
-template <int D, int DT>
+// (ragged: the grid covers the longest key range of every (sequence, head); threads past their sequence's keys leave)
+template <int D, int DT, bool VARLEN>
 __global__ __launch_bounds__(THREADS) void attn_bwd_reduce_kernel(BwdParams p, long long n_groups) {
     const long long gi = (long long)blockIdx.x * THREADS + threadIdx.x;
     if (gi >= n_groups) return;
     const int d = (int)(gi % (D / 4)) * 4;
-    const long long row = gi / (D / 4);
-    const int key = (int)(row % p.Lk);
-    const long long prob = row / p.Lk;
+    const long long grow = gi / (D / 4);
+    const int key = (int)(grow % p.Lk);
+    const long long prob = grow / p.Lk;
     const int head = (int)(prob % p.H);
     const long long oi = prob / p.H;
     const int inner = (int)(oi % p.n_inner), outer = (int)(oi / p.n_inner);
-    const long long n_prob = (long long)p.n_outer * p.n_inner * p.H;
-    const long long chunk = n_prob * p.Lk * D;                              // floats per split chunk
+    const Problem w = problem_of<VARLEN>(p, outer, head, prob);
+    if (VARLEN && key >= w.Lk) return;
+    const long long row = w.part0 + key;
+    const long long chunk = w.part_rows * D;                                // floats per split chunk
 #pragma unroll
     for (int which = 0; which < 2; ++which) {
         const float* src = p.part + (long long)which * p.n_split * chunk + row * D + d;
@@ -400,8 +441,8 @@ __global__ __launch_bounds__(THREADS) void attn_bwd_reduce_kernel(BwdParams p, l
             const float4 b = *reinterpret_cast<const float4*>(src + s * chunk);
             a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
         }
-        unsigned short* dst = which == 0 ? p.dk + head_off(p.dk_s, outer, inner, head) + (long long)key * p.dk_s[2]
-                                         : p.dv + head_off(p.dv_s, outer, inner, head) + (long long)key * p.dv_s[2];
+        unsigned short* dst = which == 0 ? p.dk + head_off(p.dk_s, outer, inner, head) + (w.k0 + key) * p.dk_s[2]
+                                         : p.dv + head_off(p.dv_s, outer, inner, head) + (w.k0 + key) * p.dv_s[2];
         uint2 w;
         w.x = GvfLp<DT>::pack(a.x, a.y);
         w.y = GvfLp<DT>::pack(a.z, a.w);
@@ -574,7 +615,7 @@ int workspace_bytes(int n_outer, int n_inner, int Lq, int Lk, int H, int D, size
     return GVF_OK;
 }
 
-template <int D, int DT>
+template <int D, int DT, bool VARLEN>
 int launch_general(const BwdParams& p0, long long problems, hipStream_t stream) {
     BwdParams p = p0;
     const long long qb = (p.Lq + XB - 1) / XB, kb = (p.Lk + XB - 1) / XB;
@@ -582,19 +623,19 @@ int launch_general(const BwdParams& p0, long long problems, hipStream_t stream) 
     const int split = key_split(problems, p.Lq, p.Lk, D);
     if (kb * problems * split > 0x7fffffffLL) return GVF_EINVAL;
     p.x_blocks = (int)qb; p.n_split = 1;
-    hipLaunchKernelGGL((attn_bwd_stats_kernel<D, DT>), dim3((unsigned)(qb * problems)), dim3(THREADS), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_stats_kernel<D, DT, VARLEN>), dim3((unsigned)(qb * problems)), dim3(THREADS), 0, stream, p);
     GVF_CHECK_LAUNCH();
     p.x_blocks = (int)kb; p.n_split = split;
-    hipLaunchKernelGGL((attn_bwd_sweep_kernel<D, true, DT>), dim3((unsigned)(kb * problems * split)), dim3(THREADS), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_sweep_kernel<D, true, DT, VARLEN>), dim3((unsigned)(kb * problems * split)), dim3(THREADS), 0, stream, p);
     GVF_CHECK_LAUNCH();
     if (split > 1) {
         const long long n_groups = problems * p.Lk * (D / 4);
         if ((n_groups + THREADS - 1) / THREADS > 0x7fffffffLL) return GVF_EINVAL;
-        hipLaunchKernelGGL((attn_bwd_reduce_kernel<D, DT>), dim3((unsigned)((n_groups + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, p, n_groups);
+        hipLaunchKernelGGL((attn_bwd_reduce_kernel<D, DT, VARLEN>), dim3((unsigned)((n_groups + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream, p, n_groups);
         GVF_CHECK_LAUNCH();
     }
     p.x_blocks = (int)qb; p.n_split = 1;
-    hipLaunchKernelGGL((attn_bwd_sweep_kernel<D, false, DT>), dim3((unsigned)(qb * problems)), dim3(THREADS), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_sweep_kernel<D, false, DT, VARLEN>), dim3((unsigned)(qb * problems)), dim3(THREADS), 0, stream, p);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
 }
@@ -609,23 +650,35 @@ int launch_bwd(const BwdParams& p, int D, hipStream_t stream) {
         GVF_CHECK_LAUNCH();
         return GVF_OK;
     }
-    return D == 32 ? launch_general<32, DT>(p, problems, stream) : launch_general<64, DT>(p, problems, stream);
+    return D == 32 ? launch_general<32, DT, false>(p, problems, stream) : launch_general<64, DT, false>(p, problems, stream);
 }
 
-}  // namespace
-
-extern "C" int gvf_attn_bwd_workspace_bytes(int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim, size_t* out) {
-    return workspace_bytes(n_outer, n_inner, Lq, Lk, H, head_dim, out);
+// Ragged form: statistics fp32 [H][total_q] twice, then (split key sweep) the partials fp32 [2][split][H][total_k][D].  The split count is
+// key_split of the host-known arguments: n_seqs * H problems of the longest lengths.
+int varlen_workspace_bytes(int n_seqs, long long total_q, long long total_k, int max_Lq, int max_Lk, int H, int D, size_t* out) {
+    if (!out || n_seqs <= 0 || max_Lq <= 0 || max_Lk <= 0 || H <= 0 || (D != 32 && D != 64)) return GVF_EINVAL;
+    if (total_q < 0 || total_k < 0 || total_q > 0x7fffffffLL || total_k > 0x7fffffffLL) return GVF_EINVAL;      // cu_seqlens are int32
+    const unsigned long long rows = (unsigned long long)H * (unsigned long long)total_q;
+    if (rows > (1ull << 40)) return GVF_EINVAL;
+    size_t bytes = 2 * gvf_align_up((size_t)rows * sizeof(float), 256);
+    const int split = key_split((long long)n_seqs * H, max_Lq, max_Lk, D);
+    if (split > 1) bytes += 2 * (size_t)split * (size_t)H * (size_t)total_k * D * sizeof(float);
+    *out = bytes;
+    return GVF_OK;
 }
 
-extern "C" int gvf_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq, void* dk,
-                            void* dv, int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim, const int64_t* q_strides,
-                            const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, const int64_t* do_strides,
-                            const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, float scale, void* workspace,
-                            size_t workspace_bytes_given, void* stream) {
-    if (dtype != GVF_DT_BF16 && dtype != GVF_DT_F16) return GVF_EINVAL;
-    size_t need = 0;
-    if (workspace_bytes(n_outer, n_inner, Lq, Lk, H, head_dim, &need) != GVF_OK) return GVF_EINVAL;
+template <int DT>
+int launch_varlen(const BwdParams& p, int D, hipStream_t stream) {
+    const long long problems = (long long)p.n_outer * p.H;
+    (void)hipGetLastError();
+    return D == 32 ? launch_general<32, DT, true>(p, problems, stream) : launch_general<64, DT, true>(p, problems, stream);
+}
+
+// The checks both entry points share (pointers, alignment, scale), and the fields they fill alike.
+int fill_params(BwdParams& p, const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq, void* dk, void* dv,
+                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, float scale,
+                void* workspace, size_t workspace_bytes_given, size_t need) {
     if (!q || !k || !v || !out || !dout || !dq || !dk || !dv || !workspace) return GVF_EINVAL;
     if (!q_strides || !k_strides || !v_strides || !o_strides || !do_strides || !dq_strides || !dk_strides || !dv_strides) return GVF_EINVAL;
     if (workspace_bytes_given < need || (((uintptr_t)workspace) & 15)) return GVF_EINVAL;
@@ -645,21 +698,72 @@ extern "C" int gvf_attn_bwd(int dtype, const void* q, const void* k, const void*
         for (int i = 0; i < 4; ++i)
             if (out_s[t][i] % 4) return GVF_EINVAL;
     }
-    BwdParams p;
     p.q = (const unsigned short*)q; p.k = (const unsigned short*)k; p.v = (const unsigned short*)v;
     p.o = (const unsigned short*)out; p.dout = (const unsigned short*)dout;
     p.dq = (unsigned short*)dq; p.dk = (unsigned short*)dk; p.dv = (unsigned short*)dv;
-    p.lse2 = (float*)workspace;
-    const size_t stat_bytes = gvf_align_up((size_t)n_outer * n_inner * H * Lq * sizeof(float), 256);
-    p.delta = (float*)((char*)workspace + stat_bytes);
-    p.part = (float*)((char*)workspace + 2 * stat_bytes);
-    p.n_outer = n_outer; p.n_inner = n_inner; p.Lq = Lq; p.Lk = Lk; p.H = H; p.x_blocks = 1; p.n_split = 1;
     for (int i = 0; i < 4; ++i) {
         p.q_s[i] = q_strides[i]; p.k_s[i] = k_strides[i]; p.v_s[i] = v_strides[i]; p.o_s[i] = o_strides[i]; p.do_s[i] = do_strides[i];
         p.dq_s[i] = dq_strides[i]; p.dk_s[i] = dk_strides[i]; p.dv_s[i] = dv_strides[i];
     }
+    p.x_blocks = 1; p.n_split = 1;
+    p.cu_q = nullptr; p.cu_k = nullptr; p.total_q = 0; p.total_k = 0;
     p.scale = scale;
     p.scale_log2e = scale * 1.4426950408889634f;
     p.inv_scale_log2e = 1.0f / p.scale_log2e;
+    return GVF_OK;
+}
+
+}  // namespace
+
+extern "C" int gvf_attn_bwd_workspace_bytes(int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim, size_t* out) {
+    return workspace_bytes(n_outer, n_inner, Lq, Lk, H, head_dim, out);
+}
+
+extern "C" int gvf_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq, void* dk,
+                            void* dv, int n_outer, int n_inner, int Lq, int Lk, int H, int head_dim, const int64_t* q_strides,
+                            const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, const int64_t* do_strides,
+                            const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, float scale, void* workspace,
+                            size_t workspace_bytes_given, void* stream) {
+    if (dtype != GVF_DT_BF16 && dtype != GVF_DT_F16) return GVF_EINVAL;
+    size_t need = 0;
+    if (workspace_bytes(n_outer, n_inner, Lq, Lk, H, head_dim, &need) != GVF_OK) return GVF_EINVAL;
+    BwdParams p;
+    if (fill_params(p, q, k, v, out, dout, dq, dk, dv, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides,
+                    dv_strides, scale, workspace, workspace_bytes_given, need) != GVF_OK)
+        return GVF_EINVAL;
+    p.lse2 = (float*)workspace;
+    const size_t stat_bytes = gvf_align_up((size_t)n_outer * n_inner * H * Lq * sizeof(float), 256);
+    p.delta = (float*)((char*)workspace + stat_bytes);
+    p.part = (float*)((char*)workspace + 2 * stat_bytes);
+    p.n_outer = n_outer; p.n_inner = n_inner; p.Lq = Lq; p.Lk = Lk; p.H = H;
     return dtype == GVF_DT_BF16 ? launch_bwd<0>(p, head_dim, (hipStream_t)stream) : launch_bwd<1>(p, head_dim, (hipStream_t)stream);
 }
+
+extern "C" int gvf_attn_varlen_bwd_workspace_bytes(int n_seqs, long long total_q, long long total_k, int max_Lq, int max_Lk, int H,
+                                                   int head_dim, size_t* out) {
+    return varlen_workspace_bytes(n_seqs, total_q, total_k, max_Lq, max_Lk, H, head_dim, out);
+}
+
+extern "C" int gvf_attn_varlen_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout, void* dq,
+                                   void* dk, void* dv, int n_seqs, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                                   long long total_q, long long total_k, int max_Lq, int max_Lk, int H, int head_dim,
+                                   const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                                   const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides,
+                                   const int64_t* dv_strides, float scale, void* workspace, size_t workspace_bytes_given, void* stream) {
+    if (dtype != GVF_DT_BF16 && dtype != GVF_DT_F16) return GVF_EINVAL;
+    size_t need = 0;
+    if (varlen_workspace_bytes(n_seqs, total_q, total_k, max_Lq, max_Lk, H, head_dim, &need) != GVF_OK) return GVF_EINVAL;
+    if (!cu_seqlens_q || !cu_seqlens_k) return GVF_EINVAL;
+    BwdParams p;
+    if (fill_params(p, q, k, v, out, dout, dq, dk, dv, q_strides, k_strides, v_strides, o_strides, do_strides, dq_strides, dk_strides,
+                    dv_strides, scale, workspace, workspace_bytes_given, need) != GVF_OK)
+        return GVF_EINVAL;
+    p.lse2 = (float*)workspace;
+    const size_t stat_bytes = gvf_align_up((size_t)H * (size_t)total_q * sizeof(float), 256);
+    p.delta = (float*)((char*)workspace + stat_bytes);
+    p.part = (float*)((char*)workspace + 2 * stat_bytes);
+    p.n_outer = n_seqs; p.n_inner = 1; p.Lq = max_Lq; p.Lk = max_Lk; p.H = H;
+    p.cu_q = cu_seqlens_q; p.cu_k = cu_seqlens_k; p.total_q = total_q; p.total_k = total_k;
+    return dtype == GVF_DT_BF16 ? launch_varlen<0>(p, head_dim, (hipStream_t)stream) : launch_varlen<1>(p, head_dim, (hipStream_t)stream);
+}
+

@@ -153,4 +153,6 @@ class SparseVAE:
 
     def training_losses(self, *a, **k):
         raise NotImplementedError("static-VAE training losses (l1 / ssim / lpips, regularisers) are outside the hot path; "
-                                  "the L1 + SSIM image loss is gvfdiffusion_amd.ops.image_loss.image_loss")
+                                  "the L1 + SSIM image loss is gvfdiffusion_amd.ops.image_loss.image_loss, and the operator the backward "
+                                  "stands on exists: sparse attention carries gradients (ops.attention_grad.attention_varlen, "
+                                  "SparseMultiHeadAttention.enable_training)")

@@ -25,6 +25,17 @@ def packed_varlen_attention(q, k, v, q_lens: List[int], kv_lens: List[int], gamm
     dt = q.dtype
     lp = precision.resolve(None, (q, k, v))
     q, k, v = (t.to(lp) for t in (q, k, v))
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        # training: the same forward kernel inside an autograd function whose backward is csrc/attn_bwd.hip's ragged form; the gradients
+        # flow on through the casts above and the unbind views of the caller's packed (possibly fp32) tensors.  QK-RMSNorm gains are
+        # applied here by the differentiable rmsnorm_heads (the kernel prologue's formula and 1e-12 floor), the kernel runs without them
+        from ...ops import attention_grad, dit_train
+        if gamma_q is not None:
+            q = dit_train.rmsnorm_heads(q, gamma_q)
+        if gamma_k is not None:
+            k = dit_train.rmsnorm_heads(k, gamma_k)
+        out = attention_grad.attention_varlen(q, k, v, _cu(q_lens, q.device), _cu(kv_lens, q.device), max(q_lens), max(kv_lens))
+        return out.to(dt)
     q, k, v = (t if (t.stride(2) == 1 and t.stride(1) == C) else t.contiguous() for t in (q, k, v))
     out = torch.empty((Tq, H, C), dtype=lp, device=q.device)
     dit_ops.attention_varlen(q, k, v, out, _cu(q_lens, q.device), _cu(kv_lens, q.device), max(q_lens), max(kv_lens), H,

@@ -5,7 +5,8 @@ the reference's model/sparse_attention/modules.py:56-185, so its state dicts loa
 How a call runs here: the projections are the 16-bit MFMA GEMM (the input's own fp16 / bf16, else ops/precision.py; fp32 accumulate, fp32 bias), the channels are viewed as
 [q|k|v][head][c] (or, with `use_old_attn_impl`, the older [head][q|k|v][c] of sparse/attention/modules.py:150-162), and the
 token lists go to the varlen flash kernel directly or after the window / serialisation gather.  QK-RMSNorm is not a separate
-pass: the per-head gains are handed to the kernel, which normalises q and k in its prologue.  RoPE is not built."""
+pass: the per-head gains are handed to the kernel, which normalises q and k in its prologue.  RoPE is not built.
+enable_training() switches forward() to the differentiable route (see there); off, the default, nothing changes."""
 from typing import *
 
 import torch
@@ -14,7 +15,11 @@ import torch.nn.functional as F
 
 from ..basic import SparseTensor
 from ..linear import linear_rows
-from .full_attn import packed_varlen_attention
+from ...ops import precision
+from ...ops.attention_grad import attention_varlen
+from ...ops.dit_train import rmsnorm_heads
+from ...ops.linear_grad import linear
+from .full_attn import _cu, packed_varlen_attention
 from .serialized_attn import SerializeMode, calc_serialization
 from .windowed_attn import calc_window_partition
 
@@ -78,6 +83,18 @@ class SparseMultiHeadAttention(nn.Module):
             self.q_rms_norm = SparseMultiHeadRMSNorm(channels // num_heads, num_heads)
             self.k_rms_norm = SparseMultiHeadRMSNorm(channels // num_heads, num_heads)
         self.to_out = nn.Linear(channels, channels)
+        self.train_forward, self.train_dtype = False, None
+
+    def enable_training(self, on: bool = True, dtype=None):
+        """With the switch on, forward() under enabled grad is differentiable in the input, the context and every parameter: the
+        projections run through ops.linear_grad.linear on the fp32 master weights (one cast per weight and forward), the QK-RMSNorm gains
+        through ops.dit_train.rmsnorm_heads, the window / serialisation gather and scatter are torch indexing, and attention is
+        ops.attention_grad.attention_varlen (csrc/attn_bwd.hip, ragged form).  Under torch.no_grad() and with the switch off (the default)
+        forward() is the inference path, unchanged.  Deliberately not keyed on module.training or requires_grad: both are on by default.
+        dtype: the 16-bit compute type (torch.float16 / torch.bfloat16); None = the input's own 16-bit type, else ops/precision.py."""
+        self.train_forward = bool(on)
+        self.train_dtype = precision.parse(dtype)
+        return self
 
     # ---- pieces ------------------------------------------------------------------------------------------------------
     def _split(self, rows: torch.Tensor, parts: int) -> List[torch.Tensor]:
@@ -111,7 +128,41 @@ class SparseMultiHeadAttention(nn.Module):
         return hit
 
     # ---- call --------------------------------------------------------------------------------------------------------
+    def _forward_train(self, x: Tokens, context: Optional[Tokens] = None) -> Tokens:
+        xr, q_lens = _rows(x)
+        lp = precision.resolve(self.train_dtype, (xr,))
+        cache = {}                                          # the 16-bit weight images of this forward
+
+        def proj(lin, rows):
+            return linear(rows.to(lp), lin.weight, lin.bias, dtype=lp, cache=cache)
+
+        gq, gk = (self.q_rms_norm.gamma, self.k_rms_norm.gamma) if self.qk_rms_norm else (None, None)
+        if self._type == "self":
+            q, k, v = self._split(proj(self.to_qkv, xr), 3)
+            fwd, bwd, seq = self._token_order(x, q_lens)
+            if fwd is not None:
+                q, k, v = q[fwd], k[fwd], v[fwd]
+            kv_seq = seq
+        else:
+            if context is None:
+                raise ValueError("cross attention needs a context")
+            cr, kv_seq = _rows(context)
+            if len(kv_seq) != len(q_lens):
+                raise AssertionError(f"Batch size mismatch, got {len(q_lens)} and {len(kv_seq)}")
+            q = proj(self.to_q, xr).reshape(xr.shape[0], self.num_heads, -1)
+            k, v = self._split(proj(self.to_kv, cr), 2)
+            bwd, seq = None, q_lens
+        if gq is not None:
+            q, k = rmsnorm_heads(q, gq), rmsnorm_heads(k, gk)
+        out = attention_varlen(q, k, v, _cu(seq, q.device), _cu(kv_seq, q.device), max(seq), max(kv_seq))
+        if bwd is not None:
+            out = out[bwd]
+        y = proj(self.to_out, out.reshape(out.shape[0], -1)).to(xr.dtype)
+        return x.replace(y) if isinstance(x, SparseTensor) else y.reshape(*x.shape[:-1], -1)
+
     def forward(self, x: Tokens, context: Optional[Tokens] = None) -> Tokens:
+        if self.train_forward and torch.is_grad_enabled():
+            return self._forward_train(x, context)
         xr, q_lens = _rows(x)
         gq, gk = self._gains()
         if self._type == "self":

@@ -45,6 +45,34 @@ int gvf_attn_bwd(int dtype, const void* q, const void* k, const void* v, const v
                  const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides,
                  float scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/*
+ * The ragged form: the gradient of gvf_attn_varlen_fwd (gvf_dit.h) without gains.  Tensors are packed [T, H, C] token lists addressed as
+ * there: 4 strides {outer (normally 0), inner (unused), seq, head}, sequence s owns token rows [cu[s], cu[s + 1]) and its element
+ * (l, h, c) sits at s * st[0] + (cu[s] + l) * st[2] + h * st[3] + c.  q, out, dout, dq have total_q rows and follow cu_seqlens_q;
+ * k, v, dk, dv have total_k rows and follow cu_seqlens_k.  cu_seqlens_* are device int32 [n_seqs + 1], non-decreasing, starting at 0
+ * and ending at the total; they are read on the device only -- no length crosses to the host, no allocation, no synchronisation.
+ * max_Lq / max_Lk (>= 1) size the grids: a value below a real length is outside the contract (rows past it get no gradient), as in
+ * the forward.  Alignment, scale, dtype and head_dim as for gvf_attn_bwd; the same host checks, plus GVF_EINVAL for a null cu_seqlens,
+ * n_seqs, H or max_L* <= 0, and a total that is negative or above 2^31 - 1.
+ *
+ * Method, rounding points and determinism are gvf_attn_bwd's: the same kernels with another problem decode (the short-sequence kernel
+ * is not used).  Workspace: lse2 and delta, fp32 [H][total_q] each (256-byte aligned), then, when the key sweep is split, its fp32
+ * partials [2][split][H][total_k][head_dim].  The split count is a function of n_seqs, H, max_Lq, max_Lk and head_dim alone: the dense
+ * rule applied to n_seqs * H problems of the longest lengths.  Every sequence's own query tiles are divided over the chunks in order; a
+ * chunk that holds none of them contributes zeros, and the chunks are summed in chunk order.
+ * Empty sequences: queries without keys get dq = +0 (the forward wrote zero output rows); keys without queries get dk = dv = +0.
+ */
+int gvf_attn_varlen_bwd_workspace_bytes(int n_seqs, long long total_q, long long total_k, int max_Lq, int max_Lk, int H, int head_dim,
+                                        size_t* out);
+
+int gvf_attn_varlen_bwd(int dtype, const void* q, const void* k, const void* v, const void* out, const void* dout,
+                        void* dq, void* dk, void* dv,
+                        int n_seqs, const int32_t* cu_seqlens_q, const int32_t* cu_seqlens_k,
+                        long long total_q, long long total_k, int max_Lq, int max_Lk, int H, int head_dim,
+                        const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                        const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides,
+                        float scale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
