@@ -69,6 +69,8 @@ SOURCES = {
     "conv3x3.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     # LPIPS pool and tap kernels: default flags
     "lpips.hip": [],
+    # static-VAE training kernels (GELU, row gather, posterior + KL, regularisers): default flags, as dit_train.hip
+    "sparse_train.hip": [],
 }
 
 

@@ -162,6 +162,15 @@ class SparseTransformerBlock(nn.Module):
         dit_ops.gemm(hid, *W["fc2"], x, dit_ops.EPI_RESID_F32)
         return x
 
+    def forward_rows_train(self, x: torch.Tensor, st: sp.SparseTensor, lp=None, cache=None, ops=None) -> torch.Tensor:
+        """The differentiable twin of forward_rows (model/sparse_voxel_diffusion/sparse_train.py): x fp32 (T, C) -> new fp32 rows, nothing in
+        place, a graph to x and to every parameter of the block.  cache: the dict that holds the 16-bit weight images of this step (one cast
+        per weight and forward; hand the same dict to every block).  ops: None = the HIP operators; a torch namespace of the same signatures
+        for a CPU check or a baseline timing.  use_checkpoint=True recomputes the block in backward (torch.utils.checkpoint, non-reentrant)."""
+        from . import sparse_train
+        lp = precision.resolve(lp, (), torch.bfloat16) if ops is None else lp
+        return sparse_train.block_rows_train(self, x, st, lp, sparse_train.resolve_ops(ops, lp, cache))
+
     def forward(self, x: sp.SparseTensor, c: torch.Tensor = None) -> sp.SparseTensor:
         rows = x.feats.float().contiguous().clone()
         return x.replace(self.forward_rows(rows, x, precision.resolve(None, (x.feats,), torch.bfloat16)).to(x.dtype))

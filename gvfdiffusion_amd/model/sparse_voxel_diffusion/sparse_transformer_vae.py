@@ -59,6 +59,7 @@ class SparseTransformerVAE(nn.Module):
         self.initialize_weights()
         self._wcache = None
         self.compute_dtype = None          # None: ops/precision.py's rule with the module default below
+        self._train_path, self._train_dtype, self._train_ops = False, None, None      # enable_training()
 
     @property
     def device(self):
@@ -118,8 +119,69 @@ class SparseTransformerVAE(nn.Module):
         out = torch.empty((T, w_out[0].shape[0]), dtype=torch.float32, device=rows.device)
         return dit_ops.gemm(hb, *w_out, out, dit_ops.EPI_STORE_F32)
 
+    # ---- training: the differentiable row path (sparse_train.py) ------------------------------------------------------------
+    def enable_training(self, on: bool = True, dtype=None, ops=None):
+        """An explicit switch, like DiT.enable_training(): with it on AND grad enabled, encode / decode / forward run the differentiable row
+        path of sparse_train.py -- fp32 `feats` with a graph to every parameter and to the input features.  Off (the default), or under
+        torch.no_grad(), every call is the inference path, bit for bit.  Not keyed on self.training or on requires_grad.
+        dtype: the 16-bit operand type of the training path (None: what _lp() resolves).  ops: None = the HIP operators; a torch namespace
+        with the same signatures (a test's CPU check, a benchmark's baseline), which may then also name torch.float32 as dtype."""
+        self._train_path = bool(on)
+        self._train_dtype = precision.parse(dtype) if (dtype is not None and ops is None) else dtype
+        self._train_ops = ops
+        return self
+
+    def training_enabled(self) -> bool:
+        return bool(getattr(self, "_train_path", False))
+
+    def _train_now(self) -> bool:
+        return self.training_enabled() and torch.is_grad_enabled()
+
+    def _train_setup(self, ops=None):
+        from . import sparse_train
+        lp = self._train_dtype if self._train_dtype is not None else self._lp()
+        if ops is None:
+            ops = sparse_train.resolve_ops(self._train_ops, lp)
+        return sparse_train, lp, ops
+
+    def _encode_train(self, x, sample_posterior, return_raw, noise, ops=None, return_kl=False):
+        T, lp, ops = self._train_setup(ops)
+        if self._train_ops is None:
+            require_cuda(x.feats, x.coords)
+        f32 = self.input_layer.weight.dtype
+        h = T.torso(self, x, x.feats.to(f32), self.input_layer, self.encoder, self.to_latent, lp, ops)
+        mean, logvar = h.chunk(2, dim=-1)
+        kl = None
+        if sample_posterior:
+            eps = torch.randn_like(mean) if noise is None else noise.to(h.dtype)
+            z, kl = ops.posterior(h, eps)
+        else:
+            z = mean
+        out = (x.replace(z), mean, logvar) if return_raw else (x.replace(z),)
+        if return_kl:
+            out = out + (kl,)
+        return out if len(out) > 1 else out[0]
+
+    def _decode_train(self, latent, ops=None):
+        T, lp, ops = self._train_setup(ops)
+        if self._train_ops is None:
+            require_cuda(latent.feats, latent.coords)
+        f32 = self.from_latent.weight.dtype
+        return latent.replace(T.torso(self, latent, latent.feats.to(f32), self.from_latent, self.decoder, self.out_layer, lp, ops))
+
+    def encode(self, x: sp.SparseTensor, sample_posterior=True, return_raw=False, noise=None):
+        """noise: the posterior's standard-normal draw, fp32 (T, latent_channels) (None: torch.randn_like) -- the training path only."""
+        if self._train_now() and x.feats.shape[0] > 0:
+            return self._encode_train(x, sample_posterior, return_raw, noise)
+        return self._encode_infer(x, sample_posterior, return_raw)
+
+    def decode(self, latent: sp.SparseTensor) -> sp.SparseTensor:
+        if self._train_now() and latent.feats.shape[0] > 0:
+            return self._decode_train(latent)
+        return self._decode_infer(latent)
+
     @torch.no_grad()
-    def encode(self, x: sp.SparseTensor, sample_posterior=True, return_raw=False):
+    def _encode_infer(self, x: sp.SparseTensor, sample_posterior=True, return_raw=False):
         require_cuda(x.feats, x.coords)
         W = self._weights()
         h = self._torso(x, x.feats, W["input"], self.encoder, W["to_latent"])
@@ -131,13 +193,23 @@ class SparseTransformerVAE(nn.Module):
         return z
 
     @torch.no_grad()
-    def decode(self, latent: sp.SparseTensor) -> sp.SparseTensor:
+    def _decode_infer(self, latent: sp.SparseTensor) -> sp.SparseTensor:
         require_cuda(latent.feats, latent.coords)
         W = self._weights()
         return latent.replace(self._torso(latent, latent.feats, W["from_latent"], self.decoder, W["out"]).to(latent.dtype))
 
-    def forward(self, x: sp.SparseTensor, t=None, c=None, mem_ratio=1.0):
-        """-> (out, mean, logvar): ElasticModule.forward around _forward_with_mem_ratio (:206-210)."""
+    def forward(self, x: sp.SparseTensor, t=None, c=None, mem_ratio=1.0, noise=None, return_kl=False):
+        """-> (out, mean, logvar): ElasticModule.forward around _forward_with_mem_ratio (:206-210).  mem_ratio is accepted and ignored.
+        On the training path (enable_training() and grad enabled) out.feats, mean and logvar are fp32 and carry the graph; noise is the
+        posterior's draw (None: randn_like) and return_kl=True appends the KL term the posterior operator computed with the sample."""
+        if self._train_now() and x.feats.shape[0] > 0:
+            _, _, ops = self._train_setup()
+            latent, mean, logvar, kl = self._encode_train(x, True, True, noise, ops=ops, return_kl=True)
+            out = self._decode_train(latent, ops=ops)
+            return (out, mean, logvar, kl) if return_kl else (out, mean, logvar)
+        if return_kl:
+            raise RuntimeError("SparseTransformerVAE.forward(return_kl=True) belongs to the training path: call enable_training() and run with "
+                               "grad enabled")
         latent, mean, logvar = self.encode(x, sample_posterior=True, return_raw=True)
         return self.decode(latent), mean, logvar
 

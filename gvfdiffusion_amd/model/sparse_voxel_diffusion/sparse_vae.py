@@ -2,7 +2,8 @@
 (model/sparse_voxel_diffusion/sparse_vae.py:60-485): owns the backbone, converts its per-voxel output rows to
 GaussianModel objects (`to_representation`), owns the renderers (`static_vae.renderers["MipGS"]`,
 inference_dpm_latent.py:161, utils/inference_utils.py:52-65) and exposes encode / decode / encode_decode[_no_render] /
-render_batch.  The loss / regularisation / snapshot members are training code and are not built."""
+render_batch.  training_losses / get_regularization_loss are the reference's (:303-362, :229-249) on the HIP loss operators, for a backbone
+on its training path (SparseTransformerVAE.enable_training()); the status / snapshot members are not built."""
 import copy
 from typing import *
 
@@ -151,8 +152,78 @@ class SparseVAE:
     def decode(self, latent):
         return self.to_representation(self.backbones["vae"].decode(latent))
 
-    def training_losses(self, *a, **k):
-        raise NotImplementedError("static-VAE training losses (l1 / ssim / lpips, regularisers) are outside the hot path; "
-                                  "the L1 + SSIM image loss is gvfdiffusion_amd.ops.image_loss.image_loss, and the operator the backward "
-                                  "stands on exists: sparse attention carries gradients (ops.attention_grad.attention_varlen, "
-                                  "SparseMultiHeadAttention.enable_training)")
+    def get_regularization_loss(self, x, reps):
+        """(:229-249) on ops.sparse_train.gaussian_reg: the RAW scaling / opacity tensors of a kind's samples are concatenated (the
+        reference concatenates the activated ones) and one launch computes both means; the activation constants are the first sample's
+        (every GaussianModel of a kind is built from one config)."""
+        from ...ops.sparse_train import gaussian_reg
+        loss, terms = 0.0, {}
+        for k, v in reps.items():
+            if k not in self.regularizations:
+                continue
+            if k not in ("GS", "MipGS"):
+                raise ValueError(f"Invalid representation type: {k}")
+            lam = self.regularizations[k]
+            if "lambda_vol" not in lam and "lambda_opacity" not in lam:
+                continue
+            g = v[0]
+            vol, opa = gaussian_reg(torch.cat([r._scaling for r in v], dim=0), torch.cat([r._opacity for r in v], dim=0), float(g.scale_bias),
+                                    float(g.opacity_bias), g.mininum_kernel_size, g.scaling_activation_type)
+            if "lambda_vol" in lam:
+                terms[f"reg_{k}_vol"] = vol
+                loss = loss + lam["lambda_vol"] * vol
+            if "lambda_opacity" in lam:
+                terms[f"reg_{k}_opacity"] = opa
+                loss = loss + lam["lambda_opacity"] * opa
+        return loss, terms
+
+    def training_losses(self, feats, image, extrinsics, intrinsics, return_aux=False, lpips=None, noise=None, **kwargs):
+        """The reference's training_losses (:303-362), same term names and return shapes: (terms, reps) or, with return_aux,
+        (terms, reps, {"rec_image", "gt_image"}).  terms: <kind>_l1 (or _l2), <kind>_ssim = 1 - ssim, <kind>_lpips, rec, kl,
+        reg_<kind>_vol, reg_<kind>_opacity, loss.  L1 and SSIM are one fused ops.image_loss call per kind, KL comes with the posterior
+        sample from ops.sparse_train.posterior, the regularisers from ops.sparse_train.gaussian_reg.  lpips: the ops.lpips.LPIPS module
+        the caller owns (with its weights: nothing is downloaded), required when lambda_lpips > 0.  noise: the posterior's draw (None:
+        randn_like).  The backbone must be on its training path (SparseTransformerVAE.enable_training())."""
+        from ...ops.image_loss import image_loss
+        vae = self.backbones["vae"]
+        if not _unwrap(vae).training_enabled():
+            raise RuntimeError("SparseVAE.training_losses: the backbone is on its inference path, whose output carries no graph -- a step would "
+                               "train nothing.  Call backbone.enable_training() first")
+        if self.lambda_lpips > 0 and lpips is None:
+            raise ValueError("SparseVAE.training_losses: lambda_lpips > 0 needs the `lpips` argument, an ops.lpips.LPIPS module with its weights "
+                             "loaded (nothing is downloaded here)")
+        if self.loss_type not in ("l1", "l2"):
+            raise ValueError(f"Invalid loss type: {self.loss_type}")
+        x, mean, logvar, kl = vae(feats, mem_ratio=self.mem_ratio, noise=noise, return_kl=True)
+        reps = self.to_representation(x)
+        for v in self.renderers.values():
+            v.rendering_options.resolution = image.shape[-1]
+        render_results = self.render_batch(reps, extrinsics, intrinsics)
+        terms = edict(loss=0.0, rec=0.0)
+        rec_image = torch.cat([v["rgb"] for v in render_results.values()])
+        gt_image = torch.cat([image for _ in render_results.values()])
+        for k, res in render_results.items():
+            rec, gt = res["rgb"], image
+            _, l1, s = image_loss(rec, gt, l1_weight=1.0, ssim_weight=self.lambda_ssim, return_terms=True)
+            if self.loss_type == "l1":
+                terms[k + "_l1"] = l1
+                terms["rec"] = terms["rec"] + l1
+            else:
+                terms[k + "_l2"] = torch.nn.functional.mse_loss(rec, gt)
+                terms["rec"] = terms["rec"] + terms[k + "_l2"]
+            if self.lambda_ssim > 0:
+                terms[k + "_ssim"] = 1 - s
+                terms["rec"] = terms["rec"] + self.lambda_ssim * terms[k + "_ssim"]
+            if self.lambda_lpips > 0:
+                terms[k + "_lpips"] = lpips(rec * 2 - 1, gt * 2 - 1)
+                terms["rec"] = terms["rec"] + self.lambda_lpips * terms[k + "_lpips"]
+            terms["loss"] = terms["loss"] + terms["rec"]
+        terms["kl"] = kl
+        terms["loss"] = terms["loss"] + self.lamda_kl * kl
+        reg_loss, reg_terms = self.get_regularization_loss(x, reps)
+        terms.update(reg_terms)
+        terms["loss"] = terms["loss"] + reg_loss
+        if return_aux:
+            # (the reference's two images, and the backbone's outputs as encode_decode's aux carries them)
+            return terms, reps, {"rec_image": rec_image, "gt_image": gt_image, "x": x, "mean": mean, "logvar": logvar}
+        return terms, reps

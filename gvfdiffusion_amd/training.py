@@ -19,7 +19,8 @@ modulate, the gated residual and the QK RMSNorm forward and backward as fused HI
 the operator above.  The block projections take torch's library GEMMs by default and, with `enable_training(linear="hip")`, this library's
 own: forward and input gradient on gvf_gemm, weight and bias gradients in fp32 from csrc/linear_grad.hip (ops/linear_grad.py), each weight
 cast once per step; the fused epilogues and row-block launches of the inference path still carry no gradient.  `diffusion_loss` is the loss of train_latent.py:183-207 on model/gaussian_diffusion.py::training_losses, ready for
-`train_step` with an ops.optim.FusedAdamW.  `DeltaHead` is the
+`train_step` with an ops.optim.FusedAdamW.  The static VAE trains as well: `SparseTransformerVAE.enable_training()` and
+`static_vae_loss` (train_vae.py:228,274: `static_vae.training_losses(...)`; model/sparse_voxel_diffusion/sparse_train.py).  `DeltaHead` is the
 smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
 per-Gaussian features, producing the (T, P, 14) deltas.
 """
@@ -133,6 +134,16 @@ def diffusion_loss(diffusion, model, latent: torch.Tensor, cond: dict, sampler=N
         t, _ = sampler.sample(latent.shape[0], latent.device)
     losses, _ = diffusion.training_losses(model, latent, t, model_kwargs=cond, noise=noise)
     return losses["loss"].mean()
+
+
+def static_vae_loss(framework, feats, image: torch.Tensor, extrinsics: torch.Tensor, intrinsics: torch.Tensor, lpips=None,
+                    noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The static-VAE loss of train_vae.py:228,274: framework.training_losses(...)[0]["loss"] for a SparseVAE whose backbone is on its
+    training path (SparseTransformerVAE.enable_training()), ready for `train_step`.  feats: the sparse input features; image (N, 3, H, W)
+    targets with their cameras; lpips: the caller's ops.lpips.LPIPS module (required when the framework's lambda_lpips > 0); noise: the
+    posterior's draw (None: drawn)."""
+    terms, _ = framework.training_losses(feats, image, extrinsics, intrinsics, lpips=lpips, noise=noise)
+    return terms["loss"]
 
 
 def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20, flat=None) -> int:
