@@ -319,3 +319,57 @@ def rast32_chain(means3D, shs, colors_precomp, opacities, scales, rotations, cov
         return _chain(_P32, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, acc, scene_kw)
     finally:
         lib32().gvfo32_set_mutant(0)
+
+
+def rast32_project(means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, *, txty_fixed=None, **scene_kw):
+    """rast64_project with every operation rounded to fp32: the yardstick of the forward's projection stage."""
+    return _project(_P32, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, txty_fixed, scene_kw)
+
+
+# ---- the forward's blend on its own (gvfo64_blend / gvfo32_blend): given records over given per-tile lists ----------------------------
+PFLAG_ALPHA, PFLAG_T, PFLAG_POWER, PFLAG_CLAMP = 1, 2, 4, 8      # the per-pixel flag byte of blend()
+
+
+def _blend(pr, rec, ranges, ids, rects, subpixel_offset, bg, H, W, form, want_power):
+    rec = pr.arr(rec)
+    P = rec.shape[0]
+    assert rec.shape == (P, 10)
+    ntiles = ((W + 15) // 16) * ((H + 15) // 16)
+    if ranges is not None:
+        ranges, ids = np.ascontiguousarray(ranges, np.int32), np.ascontiguousarray(ids, np.int32)
+        assert ranges.shape == (ntiles, 2) and (ranges[:, 0] <= ranges[:, 1]).all()
+        assert ranges.min(initial=0) >= 0 and ranges.max(initial=0) <= ids.shape[0]
+        assert ids.size == 0 or (0 <= ids.min() and ids.max() < P)
+    else:
+        rects = np.ascontiguousarray(rects, np.int32)
+        assert rects.shape == (P, 4) and not want_power
+    so, bg = pr.arr(subpixel_offset), pr.arr(bg)
+    z = lambda *s: np.zeros(s, pr.dtype)
+    out = dict(color=z(3, H, W), alpha=z(H, W), depth=z(H, W), s_color=z(3, H, W), s_alpha=z(H, W), s_depth=z(H, W),
+               flags=np.zeros((H, W), np.uint8), power=z(ids.shape[0], 16, 16) if want_power else None)
+    rc = pr.fn("blend")(P, pr.ptr(rec), None if ranges is None else _I32(ranges), None if ranges is None else _I32(ids),
+                        None if ranges is not None else _I32(rects), pr.ptr(so), pr.ptr(bg), int(H), int(W), int(form),
+                        *[pr.ptr(out[k]) for k in ("color", "alpha", "depth", "s_color", "s_alpha", "s_depth")], _U8(out["flags"]),
+                        pr.ptr(out["power"]))
+    assert rc == 0
+    return out
+
+
+def rast64_blend(rec, *, ranges=None, ids=None, rects=None, subpixel_offset=None, bg, H, W, want_power=False):
+    """The blend alone, in double precision: records rec[P,10] (x, y, conic a, b, c, opacity_eff, r, g, b, depth: rast64_project's order)
+    composited over the per-tile lists ids[ranges[t, 0]:ranges[t, 1]] in the order given, or -- lists = None -- over the lists the function
+    builds from the tile rects[P,4] (x0, y0, x1, y1; sorted by fp32 depth bits, then id).  dict(color[3,H,W], alpha, depth, the scales
+    s_color[3,H,W] = sum rgb alpha T + T_final bg, s_alpha = sum alpha T, s_depth = sum depth alpha T, flags[H,W] (PFLAG_*), power[D,16,16]
+    (want_power, explicit lists: log2 G of every list entry at every pixel of its tile))."""
+    return _blend(_P64, rec, ranges, ids, rects, subpixel_offset, bg, H, W, 0, want_power)
+
+
+def rast32_blend(rec, *, form, ranges=None, ids=None, rects=None, subpixel_offset=None, bg, H, W, want_power=False, mutant=0):
+    """rast64_blend in fp32, the yardstick.  form 0: upstream's expression (power from the conic, op * expf(power)); form 1: the device's
+    documented algorithm (scaled conic, Cholesky factor in tile-relative coordinates, exp2(log2(op) - s1^2 - s2^2)) in plain C with libm.
+    mutant (test-only, 8..11): one blend decision broken."""
+    lib32().gvfo32_set_mutant(int(mutant))
+    try:
+        return _blend(_P32, rec, ranges, ids, rects, subpixel_offset, bg, H, W, form, want_power)
+    finally:
+        lib32().gvfo32_set_mutant(0)

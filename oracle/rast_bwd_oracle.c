@@ -22,6 +22,8 @@
  * The backward is exported in its two stages, split at the accumulators: gvfo64_accumulators() (the blend's backward) and gvfo64_chain()
  * (the per-Gaussian chain rule, linear in the accumulators); gvfo64_backward() is their composition.  gvfo64_project() is the per-Gaussian
  * forward whose derivative the chain rule is.  tests/test_rast_bwd_conformance_gpu.py holds the device against each stage separately.
+ * gvfo64_blend() is the forward's compositing alone, over given records and given per-tile lists: with gvfo64_project() the reference of the
+ * forward's stage-wise conformance (tests/test_rast_fwd_conformance_gpu.py); its fp32 build has two forms, upstream's and the device's.
  * mip mode: the opacity compensation coef = sqrt(det0 / (det1 + 1e-6) + 1e-6) is differentiated exactly.
  */
 #include <stdint.h>
@@ -33,7 +35,8 @@
  * -ffp-contract=off): real = float, every operation and constant rounded to single precision, symbols gvfo32_* -- the "fp32 yardstick",
  * the same formulas as a naive single-precision composition (what a correct fp32 kernel may be expected to reach).  tgmath.h picks
  * sqrtf / expf / ... from the operand type.  -DGVFO_MUTANTS (yardstick build only): a test-only switch that breaks one line of the chain
- * rule at a time, so that tests/test_rast_bwd_ref.py can show that the conformance bar catches each of them. */
+ * rule, or one decision of the blend, at a time, so that tests/test_rast_bwd_ref.py and tests/test_rast_fwd_ref.py can show that the
+ * conformance bars catch each of them. */
 #ifdef GVFO_F32
 typedef float real;
 #define SYM(n) gvfo32_##n
@@ -50,7 +53,9 @@ void SYM(set_mutant)(int m) { g_mutant = m; }
 #define MUT(k) 0
 #endif
 /* mutants: 1 SH view-direction term of means3D dropped; 2 db[6][2] 4z -> 2z; 3 tx, ty terms of dtz dropped; 4 clamp multipliers ignored;
- * 5 depth path, y component dropped; 6 mip coefficient, dd1 term dropped; 7 first sign of gq[0] flipped */
+ * 5 depth path, y component dropped; 6 mip coefficient, dd1 term dropped; 7 first sign of gq[0] flipped;
+ * blend(): 8 skip threshold 1/256 for 1/255; 9 alpha clamp 0.995 for 0.99; 10 the T-stop applied after compositing the splat instead of in
+ * front of it; 11 every exp result times (1 + 3e-6) */
 
 #define TILE 16
 #define MODE_MIP 0
@@ -339,6 +344,166 @@ int SYM(project)(SCENE_PARAMS, const real* txty_fixed, real* out, uint8_t* out_f
         if (out_flag) out_flag[i] = (uint8_t)g.flag;
         if (out_txty) { out_txty[2 * (size_t)i] = g.tx; out_txty[2 * (size_t)i + 1] = g.ty; }
     }
+    return 0;
+}
+
+/* The blend on its own: the compositing of given per-Gaussian records over given per-tile lists -- the checker of the forward's blend
+ * (tests/test_rast_fwd_conformance_gpu.py), separated from the projection and from the binning.
+ *   rec[P][10]        the records in the order project() emits them: x, y [pixels], conic a, b, c, opacity_eff, r, g, b, depth
+ *   ranges, ids       per tile t (row-major over the ceil(W/16) x ceil(H/16) grid) the list ids[ranges[t][0] .. ranges[t][1]), composited in
+ *                     the order given.  ranges == NULL ("lists = NULL"): the function builds the lists itself from rects[P][4] = x0, y0, x1, y1
+ *                     (tiles; an empty rect = an invisible Gaussian), sorted by fp32 depth bits, then id, as pixel_list() does
+ *   subpixel_offset   [H*W][2] or NULL
+ *   form              fp32 build only (the fp64 build ignores it).  0: upstream's expression, power = -0.5 (a dx^2 + c dy^2) - b dx dy,
+ *                     alpha = op * expf(power).  1: the algorithm the device is documented to run (csrc/rast_common.h splat_cholesky /
+ *                     splat_neg_exponent), in plain C with libm: the conic pre-scaled by CONIC_K1 / CONIC_K2, its Cholesky factor
+ *                     in tile-relative coordinates, s1, s2 by fma, alpha = exp2(log2(op) - s1^2 - s2^2), a conic that is not positive definite
+ *                     dropped, T - alpha T for T (1 - alpha), the sums by fma
+ * Outputs (each may be NULL): color[3][H][W], alpha[H][W], depth[H][W]; the scales of their rounding error s_color[3][H][W] = sum rgb_c alpha T +
+ * T_final bg_c, s_alpha = sum alpha T, s_depth = sum depth alpha T (absolute values throughout); flags[H][W], the PFLAG_* bits of the decisions
+ * that sit at a threshold; power[(ranges[t][0] + k) * 256 + ly * 16 + lx] (explicit lists only): the exponent, in octaves (log2 G), of
+ * entry k of tile t's list at the tile's pixel (lx, ly), zero outside the image -- what DESIGN's accuracy claim for the Cholesky form is
+ * checked on.  Mutants 8 .. 11 (yardstick build only) break one blend decision each. */
+#define PFLAG_ALPHA 1   /* an alpha within 2e-4 (relative) of the 1/255 skip threshold */
+#define PFLAG_T     2   /* a test_T within 2e-4 (relative) of the 1e-4 termination threshold */
+#define PFLAG_POWER 4   /* a power within 1e-6 of 0 */
+#define PFLAG_CLAMP 8   /* an opacity * G within 2e-4 (relative) of the 0.99 clamp */
+
+#ifdef GVFO_F32
+typedef struct { float l11, l12, l22, c1, c2, lo; } Chol;
+/* splat_cholesky + the staged log2(opacity) of csrc/rast_blend.hip, with libm where the device has hardware instructions */
+static Chol chol_of(const float* r, float tile_x0, float tile_y0) {
+    const float K1 = -0.7213475204444817f, K2 = -1.4426950408889634f;   /* CONIC_K1 = -0.5 log2(e), CONIC_K2 = -log2(e) */
+    const float ap = r[2] * K1, bp = r[3] * K2, cp = r[4] * K1;          /* the record's a', b', c' */
+    const float m11 = -ap, m12 = -0.5f * bp, m22 = -cp;
+    const float il = 1.0f / sqrtf(m11);
+    Chol c;
+    c.l11 = m11 * il;
+    c.l12 = m12 * il;
+    const float d = m22 - c.l12 * c.l12;
+    c.l22 = sqrtf(d);
+    const int ok = m11 > 0.0f && d > 0.0f && m11 < INFINITY && d < INFINITY;
+    if (!ok) { c.l11 = 0.0f; c.l12 = 0.0f; c.l22 = 0.0f; }
+    const float xr = r[0] - tile_x0, yr = r[1] - tile_y0;
+    c.c1 = ok ? fmaf(c.l11, xr, c.l12 * yr) : 0.0f;
+    c.c2 = ok ? c.l22 * yr : 0.0f;
+    c.lo = ok ? log2f(r[5]) : -INFINITY;
+    return c;
+}
+#endif
+
+int SYM(blend)(int P, const real* rec, const int32_t* ranges, const int32_t* ids, const int32_t* rects, const real* subpixel_offset,
+               const real* bg, int H, int W, int form, real* out_color, real* out_alpha, real* out_depth, real* s_color, real* s_alpha,
+               real* s_depth, uint8_t* out_flags, real* out_power) {
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    const real thr = MUT(8) ? 1.0 / 256.0 : 1.0 / 255.0, clampv = MUT(9) ? 0.995 : 0.99, expmul = MUT(11) ? 1.0 + 3e-6 : 1.0;
+    DI* built = ranges ? NULL : (DI*)malloc(sizeof(DI) * (size_t)(P > 0 ? P : 1));
+#ifdef GVFO_F32
+    int longest = P > 0 ? P : 1;                    /* (a given list may hold duplicates: it is what is being checked) */
+    if (ranges) for (int t = 0; t < gx * gy; ++t) if (ranges[2 * t + 1] - ranges[2 * t] > longest) longest = ranges[2 * t + 1] - ranges[2 * t];
+    Chol* ch = (Chol*)malloc(sizeof(Chol) * (size_t)longest);
+#else
+    (void)form;
+#endif
+    for (int ty = 0; ty < gy; ++ty)
+        for (int tx = 0; tx < gx; ++tx) {
+            const int t = ty * gx + tx;
+            int n = 0, first = 0;
+            if (ranges) { first = ranges[2 * t]; n = ranges[2 * t + 1] - first; }
+            else {
+                for (int i = 0; i < P; ++i) {
+                    const int32_t* r = rects + 4 * (size_t)i;
+                    if (tx >= r[0] && tx < r[2] && ty >= r[1] && ty < r[3]) { built[n].depth = rec[10 * (size_t)i + 9]; built[n].id = i; ++n; }
+                }
+                qsort(built, (size_t)n, sizeof(DI), di_cmp);
+            }
+#define ENTRY(k) (ranges ? (int)ids[first + (k)] : built[k].id)
+#ifdef GVFO_F32
+            if (form == 1) for (int k = 0; k < n; ++k) ch[k] = chol_of(rec + 10 * (size_t)ENTRY(k), (float)(tx * TILE), (float)(ty * TILE));
+#endif
+            for (int ly = 0; ly < TILE; ++ly)
+                for (int lx = 0; lx < TILE; ++lx) {
+                    const int px = tx * TILE + lx, py = ty * TILE + ly;
+                    if (px >= W || py >= H) {
+                        if (out_power && ranges) for (int k = 0; k < n; ++k) out_power[(size_t)(first + k) * 256 + ly * TILE + lx] = 0;
+                        continue;
+                    }
+                    const size_t pid = (size_t)py * W + px;
+                    real pxf = (real)px, pyf = (real)py;
+                    if (subpixel_offset) { pxf += subpixel_offset[2 * pid]; pyf += subpixel_offset[2 * pid + 1]; }
+                    real T = 1.0, C[3] = {0, 0, 0}, D = 0, SC[3] = {0, 0, 0}, SA = 0, SD = 0;
+                    int fl = 0, stopped = 0;
+                    for (int k = 0; k < n; ++k) {
+                        const real* q = rec + 10 * (size_t)ENTRY(k);
+                        real power_oct, araw;          /* log2 G, opacity * G */
+                        int skip = 0;
+#ifdef GVFO_F32
+                        if (form == 1) {
+                            const Chol* c = &ch[k];
+                            const float pxr = pxf - (float)(tx * TILE), pyr = pyf - (float)(ty * TILE);
+                            const float s1 = fmaf(-c->l11, pxr, fmaf(-c->l12, pyr, c->c1));
+                            const float s2 = fmaf(-c->l22, pyr, c->c2);
+                            power_oct = -fmaf(s2, s2, s1 * s1);
+                            araw = exp2f(-fmaf(s2, s2, fmaf(s1, s1, -c->lo))) * expmul;
+                        } else
+#endif
+                        {
+                            const real dx = q[0] - pxf, dy = q[1] - pyf;
+                            const real power = -0.5 * (q[2] * dx * dx + q[4] * dy * dy) - q[3] * dx * dy;
+                            power_oct = power * (real)1.4426950408889634;
+                            skip = power > 0.0;
+                            araw = q[5] * (exp(power) * expmul);
+                        }
+                        if (out_power && ranges) out_power[(size_t)(first + k) * 256 + ly * TILE + lx] = power_oct;
+                        if (stopped) continue;         /* (the exponents of the whole list are reported) */
+                        if (fabs(power_oct) < (real)1e-6) fl |= PFLAG_POWER;
+                        if (skip) continue;
+                        if (fabs(araw - (real)(1.0 / 255.0)) < (real)2e-4 * (real)(1.0 / 255.0)) fl |= PFLAG_ALPHA;
+                        if (fabs(araw - (real)0.99) < (real)2e-4 * (real)0.99) fl |= PFLAG_CLAMP;
+                        const real alpha = fmin(clampv, araw);
+                        if (alpha < thr) continue;
+                        real w = alpha * T, test_T;
+#ifdef GVFO_F32
+                        if (form == 1) test_T = T - w; else
+#endif
+                            test_T = T * ((real)1.0 - alpha);
+                        if (fabs(test_T - (real)0.0001) < (real)2e-4 * (real)0.0001) fl |= PFLAG_T;
+                        if (test_T < (real)0.0001) { stopped = 1; if (!MUT(10)) continue; }
+#ifdef GVFO_F32
+                        if (form == 1) {
+                            for (int c = 0; c < 3; ++c) C[c] = fmaf(q[6 + c], w, C[c]);
+                            D = fmaf(q[9], w, D);
+                        } else
+#endif
+                        {
+                            for (int c = 0; c < 3; ++c) C[c] += q[6 + c] * alpha * T;
+                            D += q[9] * alpha * T;
+                        }
+                        for (int c = 0; c < 3; ++c) SC[c] += fabs(q[6 + c]) * w;
+                        SA += w; SD += fabs(q[9]) * w;
+                        T = test_T;
+                    }
+                    const size_t hw = (size_t)H * W;
+                    for (int c = 0; c < 3; ++c) {
+#ifdef GVFO_F32
+                        if (out_color) out_color[c * hw + pid] = form == 1 ? fmaf(T, bg[c], C[c]) : C[c] + T * bg[c];
+#else
+                        if (out_color) out_color[c * hw + pid] = C[c] + T * bg[c];
+#endif
+                        if (s_color) s_color[c * hw + pid] = SC[c] + T * fabs(bg[c]);
+                    }
+                    if (out_alpha) out_alpha[pid] = (real)1.0 - T;
+                    if (out_depth) out_depth[pid] = D;
+                    if (s_alpha) s_alpha[pid] = SA;
+                    if (s_depth) s_depth[pid] = SD;
+                    if (out_flags) out_flags[pid] = (uint8_t)fl;
+                }
+#undef ENTRY
+        }
+#ifdef GVFO_F32
+    free(ch);
+#endif
+    free(built);
     return 0;
 }
 
