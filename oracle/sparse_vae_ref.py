@@ -7,6 +7,9 @@ the absolute position embedder :73-112; the swin window partition sparse/attenti
 attention inside a window with scale head_dim^-0.5 (flash_attn_varlen_qkvpacked_func, a third-party kernel -- restated
 from its definition); tanh-GELU MLP :115-126.  Operates on (feats (T, C), coords (T, 4) = batch, x, y, z).
 Pinned by tests/golden/sparse_vae_golden.npz (outputs of the reference classes imported in the build container).
+attention_spans / multi_head_attention / block over spans / block_attn_rule / torso_spans restate the same computation over explicit
+(batch, key rows, write rows) spans -- serialised windows, whose keys overlap, and all five attn_modes of block_attn_config
+(sparse_transformer.py:11-25); the spans come from tests/sparse_ref.py, which is pinned by tests/golden/sparse_index_golden.npz.
 
 precision "bf16" / "fp16" rounds where the HIP path rounds: every GEMM / attention operand (LayerNorm outputs, q k v, the
 probabilities' numerators, the attention output, the GELU output) to that type, fp32 everywhere else."""
@@ -61,20 +64,68 @@ def attention_groups(q, k, v, gid, precision):
     return out
 
 
-def block(x, gid, sd, prefix, heads, precision, old_impl, qk_rms_norm=False):
-    T, C = x.shape
-    d = C // heads
-    h = _r(F.layer_norm(x, (C,), eps=1e-6), precision)
-    qkv = _r(_lin(h, sd, prefix + ".attn.to_qkv", precision), precision)
+def attention_spans(q, k, v, spans, precision):
+    """q (Tq, H, d), k v (Tk, H, d); spans: a list of (batch, key rows, write rows), index tensors into k / v and into q.  Softmax attention
+    of each span's write rows over its key rows, in the order given; the output is taken at the write rows only (a serialised window
+    gathers `window_size` key rows and writes back its valid span: sparse/attention/serialized_attn.py).  Rows no span writes stay zero; a
+    row two spans write holds the later one's.  float64 inputs with precision "fp32": the reference; "bf16" / "fp16": attention_groups'
+    rounding placement."""
+    out = torch.zeros_like(q)
+    d = q.shape[-1]
+    for _, keys, writes in spans:
+        qg = q[writes].permute(1, 0, 2)                                             # (H, n_w, d)
+        kg, vg = k[keys].permute(1, 0, 2), v[keys].permute(1, 0, 2)                 # (H, n_k, d)
+        s = (qg @ kg.transpose(-1, -2)) * d ** -0.5
+        if precision in _LP:
+            e = torch.exp(s - s.amax(dim=-1, keepdim=True))
+            o = (_r(e, precision) @ vg) / e.sum(dim=-1, keepdim=True)
+        else:
+            o = torch.softmax(s, dim=-1) @ vg
+        out[writes] = o.permute(1, 0, 2)
+    return out
+
+
+def _attend(q, k, v, groups, precision):
+    """groups: a group id per token (attention_groups) or a list of spans (attention_spans)"""
+    if isinstance(groups, (list, tuple)):
+        return attention_spans(q, k, v, groups, precision)
+    return attention_groups(q, k, v, groups, precision)
+
+
+def _heads(rows, parts, heads, old_impl):
+    """(T, parts * C) projection rows -> `parts` tensors (T, H, d): channels [head][part][c] (old_impl) or [part][head][c]
+    (sparse/attention/modules.py:150-162)"""
+    T = rows.shape[0]
     if old_impl:
-        q, k, v = qkv.reshape(T, heads, 3 * d).chunk(3, dim=-1)
+        return rows.reshape(T, heads, parts, -1).unbind(dim=2)
+    return rows.reshape(T, parts, heads, -1).unbind(dim=1)
+
+
+def multi_head_attention(h, groups, sd, prefix, heads, precision, old_impl, qk_rms_norm=False, context=None, round_output=False):
+    """SparseMultiHeadAttention (sparse/attention/modules.py:72-185) on rows h (T, C) -> (T, C): to_qkv (or, with a context (Tc, Cc), to_q
+    and to_kv; the spans' key rows then index the context), the channel layout, optional QK-RMSNorm, attention per group / span, to_out.
+    round_output: the closing projection's result is 16-bit too (torch.autocast's placement, which the module's enable_training() route
+    follows; the inference route and the blocks keep it fp32)."""
+    T, C = h.shape
+    d = C // heads
+    if context is None:
+        q, k, v = _heads(_r(_lin(h, sd, prefix + ".to_qkv", precision), precision), 3, heads, old_impl)
     else:
-        q, k, v = qkv.reshape(T, 3, heads, d).unbind(dim=1)
+        q = _r(_lin(h, sd, prefix + ".to_q", precision), precision).reshape(T, heads, d)
+        k, v = _heads(_r(_lin(context, sd, prefix + ".to_kv", precision), precision), 2, heads, old_impl)
     if qk_rms_norm:   # SparseMultiHeadRMSNorm, trellis/modules/sparse/attention/modules.py:11-25: normalize * gamma * sqrt(d)
-        q = _r(F.normalize(q, dim=-1) * sd[prefix + ".attn.q_rms_norm.gamma"] * d ** 0.5, precision)
-        k = _r(F.normalize(k, dim=-1) * sd[prefix + ".attn.k_rms_norm.gamma"] * d ** 0.5, precision)
-    a = _r(attention_groups(q, k, v, gid, precision).reshape(T, C), precision)
-    x = x + _lin(a, sd, prefix + ".attn.to_out", precision)
+        q = _r(F.normalize(q, dim=-1) * sd[prefix + ".q_rms_norm.gamma"] * d ** 0.5, precision)
+        k = _r(F.normalize(k, dim=-1) * sd[prefix + ".k_rms_norm.gamma"] * d ** 0.5, precision)
+    a = _r(_attend(q, k, v, groups, precision).reshape(T, C), precision)
+    y = _lin(a, sd, prefix + ".to_out", precision)
+    return _r(y, precision) if round_output else y
+
+
+def block(x, gid, sd, prefix, heads, precision, old_impl, qk_rms_norm=False):
+    """gid: a group id per token, or a list of spans (attention_spans)."""
+    T, C = x.shape
+    h = _r(F.layer_norm(x, (C,), eps=1e-6), precision)
+    x = x + multi_head_attention(h, gid, sd, prefix + ".attn", heads, precision, old_impl, qk_rms_norm)
     h = _r(F.layer_norm(x, (C,), eps=1e-6), precision)
     h = _r(F.gelu(_lin(h, sd, prefix + ".mlp.mlp.0", precision), approximate="tanh"), precision)
     return x + _lin(h, sd, prefix + ".mlp.mlp.2", precision)
@@ -90,6 +141,50 @@ def _torso(rows, coords, sd, cfg, first, stack, last, precision):
     if cfg.get("norm_output", False):
         x = F.layer_norm(x, (C,))
     return _lin(x, sd, last, precision)
+
+
+ORDERS = ("Z_ORDER", "Z_ORDER_TRANSPOSED", "HILBERT", "HILBERT_TRANSPOSED")
+
+
+def block_attn_rule(cfg, i):
+    """Block i's attention plan, restated from block_attn_config (sparse_transformer.py:11-25): a dict with kind "full" | "windowed" |
+    "serialized", window, shift (windowed: one integer for the three axes), shift_sequence, shift_window, order (a name of ORDERS)."""
+    mode, w = cfg.get("attn_mode", "swin"), cfg["window_size"]
+    if mode == "swin":
+        return dict(kind="windowed", window=w, shift=w // 2 * (i % 2))
+    if mode == "full":
+        return dict(kind="full")
+    rule = dict(kind="serialized", window=w, shift_sequence=0, shift_window=(0, 0, 0), order="Z_ORDER")
+    if mode == "shift_window":
+        rule["shift_window"] = (16 * (i % 2),) * 3
+    elif mode == "shift_sequence":
+        rule["shift_sequence"] = w // 2 * (i % 2)
+    elif mode == "shift_order":
+        rule["order"] = ORDERS[i % 4]
+    else:
+        raise ValueError(f"unknown attn_mode {mode}")
+    return rule
+
+
+def torso_spans(rows, coords, sd, cfg, first, stack, last, precision, make_spans):
+    """_torso for all five attn_modes: block i attends over make_spans(block_attn_rule(cfg, i)), a list of spans (attention_spans) that
+    the caller builds from the coordinates (tests/sparse_ref.py::spans_of_rule: the curve codes come from the C oracle)."""
+    C, heads = cfg["model_channels"], cfg["num_heads"]
+    assert cfg.get("pe_mode", "ape") == "ape"
+    x = _lin(rows, sd, first, precision) + ape(coords[:, 1:], C).to(rows.dtype)
+    for i in range(cfg["num_blocks"]):
+        x = block(x, make_spans(block_attn_rule(cfg, i)), sd, f"{stack}.{i}", heads, precision, cfg.get("use_old_attn_impl", True))
+    if cfg.get("norm_output", False):
+        x = F.layer_norm(x, (C,))
+    return _lin(x, sd, last, precision)
+
+
+def encode_spans(sd, cfg, feats, coords, make_spans, precision="fp32"):
+    return torso_spans(feats, coords, sd, cfg, "input_layer", "encoder", "to_latent", precision, make_spans).chunk(2, dim=-1)
+
+
+def decode_spans(sd, cfg, z, coords, make_spans, precision="fp32"):
+    return torso_spans(z, coords, sd, cfg, "from_latent", "decoder", "out_layer", precision, make_spans)
 
 
 def encode(sd, cfg, feats, coords, precision="fp32"):
