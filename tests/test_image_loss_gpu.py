@@ -1,6 +1,8 @@
 """The fused L1 + SSIM image loss (ops/image_loss.py -> gvf_image_loss_forward / _backward) on an MI355X: value and gradient against the
-float64 oracle (tests/ssim_ref.py) and the reference's golden, with bars calibrated by an fp32 torch composition of the same formula;
-the L1-only case against torch; identical images; determinism; refusals; and the loss through the batched renderer in training."""
+float64 oracle (tests/ssim_ref.py) and the reference's golden, with bars calibrated by an fp32 torch composition of the same formula
+(computed on host copies: ssim_ref.ssim_torch32 / loss_torch32 return host tensors, and every comparison below is made on the host);
+the L1-only case against torch; identical images; determinism; refusals; and the loss through the batched renderer in training.
+The element-wise measure of the same kernels is tests/test_image_loss_conformance_gpu.py."""
 import math
 import os
 
