@@ -71,6 +71,8 @@ SOURCES = {
     "lpips.hip": [],
     # static-VAE training kernels (GELU, row gather, posterior + KL, regularisers): default flags, as dit_train.hip
     "sparse_train.hip": [],
+    # motion-VAE training kernels (GEGLU, embedding, grouped posterior + KL): default flags, as sparse_train.hip
+    "vae_train.hip": [],
 }
 
 

@@ -31,7 +31,7 @@ from ..ops import precision
 
 class GEGLU(nn.Module):
     def forward(self, x):  # parameter-less placeholder keeping `net.2` at index 2 (model/autoencoder.py:90-93)
-        raise RuntimeError("GEGLU runs inside gvf_geglu_bf16; call GSKLTemporalVariationalAutoEncoder.decode")
+        raise RuntimeError("GEGLU runs inside gvf_geglu (inference) or ops.vae_train.geglu (training); call GSKLTemporalVariationalAutoEncoder.decode")
 
 
 class FeedForward(nn.Module):
@@ -133,6 +133,7 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
         nn.init.zeros_(self.to_outputs.weight)       # zero_module(to_outputs), model/autoencoder.py:434
         nn.init.zeros_(self.to_outputs.bias)
         self._wcache = None
+        self._train = None                           # enable_training(): the state of the differentiable route (model/autoencoder_train.py)
         self.compute_dtype = None                    # None: ops/precision.py decides per call (GVF_DIT_DTYPE, an autocast region -- the
                                                      # reference decodes under accelerate's fp16 autocast, inference_dpm_latent.py:256 --, else bf16)
         self.max_chunk_rows = (1 << 20) + (1 << 16)  # hard cap on the rows (B*T*Pc) of the 16-bit attention-output chunk: 1.6 GiB at dim 768 (released config: 6 chunks of <= 45056 Gaussians x 24 frames)
@@ -144,6 +145,28 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
 
     def _lp(self):
         return precision.resolve(self.compute_dtype, (), torch.bfloat16)
+
+    def enable_training(self, on=True, dtype=None, ops=None, use_checkpoint=True):
+        """Switch the differentiable route on or off.  On AND with grad enabled, encode / decode_latents / decode / forward run
+        model/autoencoder_train.py (every operator a HIP forward and backward, gradients to the fp32 parameters, to `queries` and to the
+        latents); off, or under torch.no_grad(), they are the inference code, bit for bit, which builds no graph.  dtype: the 16-bit
+        operand type (None: set_compute_dtype / ops/precision.py's rule); ops: another operator namespace (tests, baselines; None: the HIP
+        operators); use_checkpoint: each chunk of `chunk_size` queries is recomputed in the backward instead of kept."""
+        from .autoencoder_train import TrainState
+        self._train = TrainState(dtype, ops, use_checkpoint) if on else None
+        return self
+
+    def _training_route(self):
+        return self._train is not None and torch.is_grad_enabled()
+
+    def encode_rows(self, static_pc, delta_pc, input_static_gs, est, noise=None):
+        """The differentiable part of encode on given samples: input_static_gs (B,L,3) the sampled Gaussians' xyz, est (B,T,L,3) their
+        interpolated motion (compute_delta_interp), noise (B*T*L, latent_dim) or None (drawn) -> (kl [B*T], z, posterior).  Needs
+        enable_training() and grad enabled."""
+        if not self._training_route():
+            raise RuntimeError("encode_rows is the training route: call enable_training() and run with grad enabled")
+        from . import autoencoder_train
+        return autoencoder_train.encode_rows(self, static_pc, delta_pc, input_static_gs, est, noise)
 
     # ---- encode (encode_latent.py / training; not on the inference path) ---------------------------------------------
     @staticmethod
@@ -171,11 +194,18 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
         nb0 = torch.gather(micro_static_pc, 1, knn_idx.reshape(B, L * K, 1).expand(B, L * K, 3)).reshape(B, 1, L, K, 3)
         return ((nb - nb0) * w[:, None, :, :, None]).sum(dim=3)
 
-    @torch.no_grad()
-    def encode(self, static_pc, delta_pc, static_gs_list, random_start: bool = True, sample_posterior: bool = True):
+    def encode(self, static_pc, delta_pc, static_gs_list, random_start: bool = True, sample_posterior: bool = True, noise=None):
         """static_pc (B,N,3), delta_pc (B,T,N,3), static_gs_list [ (N_gs,14) ] -> (kl, x, posterior, sampled_static_gs)
         (model/autoencoder.py:502-550).  random_start=False makes the farthest point sampling start at each sample's
-        first Gaussian (upstream's default is a random start)."""
+        first Gaussian (upstream's default is a random start).  On the training route (enable_training(), grad enabled) the posterior is
+        always sampled, with `noise` (B*T*L, latent_dim) when given, and kl is the fp32 [B*T] vector of the HIP operator."""
+        if self._training_route():
+            from . import autoencoder_train
+            return autoencoder_train.encode(self, static_pc, delta_pc, static_gs_list, random_start=random_start, noise=noise)
+        return self._encode_inference(static_pc, delta_pc, static_gs_list, random_start, sample_posterior)
+
+    @torch.no_grad()
+    def _encode_inference(self, static_pc, delta_pc, static_gs_list, random_start, sample_posterior):
         from ..utils.points import sample_gs
         _lib.require_cuda(static_pc, delta_pc)
         W = self._weights()
@@ -224,8 +254,12 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
         from ..utils.points import pad_static_gs
         return pad_static_gs(static_gs)
 
-    def forward(self, static_gs, static_pc, delta_pc, **kw):
-        """encode -> decode over the padded static Gaussians (model/autoencoder.py:621-627; same argument order)."""
+    def forward(self, static_gs, static_pc, delta_pc, noise=None, **kw):
+        """encode -> decode over the padded static Gaussians (model/autoencoder.py:621-627; same argument order).  On the training route
+        `logits` carries the graph; noise: the posterior's draw (None: drawn)."""
+        if self._training_route():
+            from . import autoencoder_train
+            return autoencoder_train.forward(self, static_gs, static_pc, delta_pc, noise=noise, **kw)
         kl, x, posterior, _ = self.encode(static_pc, delta_pc, static_gs, **kw)
         padded, _ = self.pad_static_gs(static_gs)
         return {"logits": self.decode(x, padded).squeeze(-1), "kl": kl, "posterior": posterior}
@@ -281,9 +315,15 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
         return W
 
     # ---- decode ------------------------------------------------------------------------------------------
-    @torch.no_grad()
     def decode_latents(self, x: torch.Tensor) -> torch.Tensor:
         """proj + `depth` latent self-attention / GEGLU blocks: (B*T, L, latent_dim) -> fp32 (B*T*L, dim)."""
+        if self._training_route():
+            from . import autoencoder_train
+            return autoencoder_train.decode_latents(self, x)
+        return self._decode_latents_inference(x)
+
+    @torch.no_grad()
+    def _decode_latents_inference(self, x: torch.Tensor) -> torch.Tensor:
         _lib.require_cuda(x)
         W = self._weights()
         BT, L, Dl = x.shape
@@ -309,9 +349,15 @@ class GSKLTemporalVariationalAutoEncoder(nn.Module):
             dit_ops.gemm_bf16(act, *w["fc2"], h, dit_ops.EPI_RESID_F32)
         return h
 
-    @torch.no_grad()
     def decode(self, x: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
         """x: (B*T, L, latent_dim), queries: (B, P, gs_dim) -> (B, T, P, output_dim)  (model/autoencoder.py:579-609)."""
+        if self._training_route():
+            from . import autoencoder_train
+            return autoencoder_train.decode(self, x, queries)
+        return self._decode_inference(x, queries)
+
+    @torch.no_grad()
+    def _decode_inference(self, x: torch.Tensor, queries: torch.Tensor) -> torch.Tensor:
         _lib.require_cuda(x, queries)
         W = self._weights()
         B, P = queries.shape[:2]

@@ -20,7 +20,9 @@ the operator above.  The block projections take torch's library GEMMs by default
 own: forward and input gradient on gvf_gemm, weight and bias gradients in fp32 from csrc/linear_grad.hip (ops/linear_grad.py), each weight
 cast once per step; the fused epilogues and row-block launches of the inference path still carry no gradient.  `diffusion_loss` is the loss of train_latent.py:183-207 on model/gaussian_diffusion.py::training_losses, ready for
 `train_step` with an ops.optim.FusedAdamW.  The static VAE trains as well: `SparseTransformerVAE.enable_training()` and
-`static_vae_loss` (train_vae.py:228,274: `static_vae.training_losses(...)`; model/sparse_voxel_diffusion/sparse_train.py).  `DeltaHead` is the
+`static_vae_loss` (train_vae.py:228,274: `static_vae.training_losses(...)`; model/sparse_voxel_diffusion/sparse_train.py).  So does the
+motion VAE: `GSKLTemporalVariationalAutoEncoder.enable_training()` and `motion_vae_loss` (train_vae.py:295-334: KL + interpolation + render
+loss on the decoder's `pred_delta`; model/autoencoder_train.py).  `DeltaHead` is the
 smallest such module: the decoder's last projection (model/autoencoder.py `to_outputs`) as a plain torch layer over given
 per-Gaussian features, producing the (T, P, 14) deltas.
 """
@@ -144,6 +146,37 @@ def static_vae_loss(framework, feats, image: torch.Tensor, extrinsics: torch.Ten
     posterior's draw (None: drawn)."""
     terms, _ = framework.training_losses(feats, image, extrinsics, intrinsics, lpips=lpips, noise=noise)
     return terms["loss"]
+
+
+def motion_vae_loss(model, renderer, gaussians: Sequence, micro_static_pc: torch.Tensor, micro_delta_pc: torch.Tensor, extrinsics: torch.Tensor,
+                    intrinsics: torch.Tensor, targets: torch.Tensor, frame_of_view: Optional[Sequence[Sequence[int]]] = None,
+                    kl_weight: float = 1e-5, xyz_loss_weight: float = 0.1, l1_weight: float = 1.0, ssim_weight: float = 0.2, lpips=None,
+                    lpips_weight: float = 1.0, knn_k: int = 8, beta: float = 7.0, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The motion-VAE part of the reference's joint step (train_vae.py:295-334, default weights of :40-47) for a
+    GSKLTemporalVariationalAutoEncoder on its training route (enable_training()), ready for `train_step`:
+        kl.mean() * kl_weight + interpolation_loss * xyz_loss_weight + render loss (L1 + SSIM [+ LPIPS]) of the deformed Gaussians
+    gaussians: the B static GaussianModels (their (P_b, 14) tensors are the decoder's queries); micro_static_pc (B, N, 3), micro_delta_pc
+    (B, T, N, 3); extrinsics (B, V, 4, 4), intrinsics (3, 3) or (B, 3, 3), targets (B, V, 3, H, W); frame_of_view[b][v]: the frame view v of
+    sample b shows (default v).  The LPIPS term needs the caller's ops.lpips.LPIPS module, as in render_loss_frames; the render loss is the
+    mean over the samples of each sample's loss over its V views (the reference's loss over the stacked B * V views)."""
+    from .utils.points import get_gaussian_tensor
+    static_gs = [get_gaussian_tensor(g) for g in gaussians]
+    out = model(static_gs, micro_static_pc, micro_delta_pc, noise=noise)
+    pred = out["logits"]                                                  # (B, T, max P_b, 14)
+    if pred.grad_fn is None:
+        raise RuntimeError("motion_vae_loss: the model's output carries no graph (call enable_training() and run with grad enabled)")
+    loss = out["kl"].mean() * kl_weight
+    moving = micro_static_pc[:, None] + micro_delta_pc
+    interp, _, _ = interpolation_loss(static_gs, micro_static_pc, moving, pred, knn_k=knn_k, beta=beta)
+    loss = loss + interp * xyz_loss_weight
+    B = len(gaussians)
+    render = 0.0
+    for b in range(B):
+        deltas = pred[b, :, :static_gs[b].shape[0]].contiguous()
+        render = render + render_loss_frames(renderer, gaussians[b], extrinsics[b], intrinsics if intrinsics.dim() == 2 else intrinsics[b], deltas,
+                                             targets[b], None if frame_of_view is None else frame_of_view[b], l1_weight=l1_weight,
+                                             ssim_weight=ssim_weight, lpips=lpips, lpips_weight=lpips_weight)
+    return loss + render / B
 
 
 def allreduce_gradients(params: Iterable[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20, flat=None) -> int:
