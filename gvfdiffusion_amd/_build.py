@@ -73,6 +73,8 @@ SOURCES = {
     "sparse_train.hip": [],
     # motion-VAE training kernels (GEGLU, embedding, grouped posterior + KL): default flags, as sparse_train.hip
     "vae_train.hip": [],
+    # submanifold sparse 3x3x3 convolution: the gemm.hip / conv3x3.hip flags (4 to 16 accumulators per wave in VGPRs)
+    "spconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

@@ -4,6 +4,7 @@ vox2seq voxel serialisation, the full / windowed / serialized sparse attention o
 from . import vox2seq  # noqa: F401
 from .basic import *   # noqa: F401,F403
 from .linear import SparseLinear  # noqa: F401
+from .conv import SparseConv3d, SparseInverseConv3d  # noqa: F401
 from .nonlinearity import *  # noqa: F401,F403
 from .norm import *  # noqa: F401,F403
 from .spatial import *  # noqa: F401,F403
