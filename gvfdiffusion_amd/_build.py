@@ -75,6 +75,8 @@ SOURCES = {
     "vae_train.hip": [],
     # submanifold sparse 3x3x3 convolution: the gemm.hip / conv3x3.hip flags (4 to 16 accumulators per wave in VGPRs)
     "spconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # dense 3x3x3 convolution + occupancy read-out: the spconv.hip flags (1 to 16 accumulators per wave in VGPRs)
+    "conv3d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from ... import sparse as sp
 from ...model.sparse_voxel_diffusion.sparse_transformer import AbsolutePositionEmbedder, SparseFeedForward, token_partition
-from ...ops import dit_ops, precision, spconv
+from ...ops import conv3d, dit_ops, precision, spconv
 from ...sparse.attention.modules import SparseMultiHeadAttention
 from ...sparse.conv import neighbor_map
 
@@ -95,6 +95,56 @@ class HipOps:
         wimg, bias = conv.packed(self.lp)
         return spconv.conv3(a16, nbr, wimg, conv.conv.out_channels, bias=bias, addend=addend, cin=conv.conv.in_channels)
 
+    def dense_conv3(self, a16, grid, conv, addend=None, store="rows"):
+        """a16 16-bit rows of the dense (B, X, Y, Z) grid (zeros in the columns up to the next multiple of 32), conv: an nn.Conv3d(cin, cout,
+        3, padding=1) -> fp32 rows, or under store="shuffle2" the fp32 rows of pixel_shuffle_3d(., 2); `addend` (fp32) added in the epilogue.
+        The weight image is packed once per (module, operand type) and parameter version.
+
+        Routing (measured): where both channel counts are multiples of 64 and the submanifold kernel's launch on these
+        rows fills the card's 256 compute units, the convolution goes through gvf_spconv3 on the full grid's neighbour map (built once per
+        grid) and the pixel-shuffle becomes a permuting copy; every other shape takes the dense kernel, shuffle in its store."""
+        w, b = conv.weight, conv.bias
+        cin, cout = conv.in_channels, conv.out_channels
+        sub = self.spconv_route(a16.shape[0], cin, cout) and max(grid[1:]) <= 1024      # the neighbour map's coordinate range
+        key = (id(w), self.lp, "spconv3" if sub else "conv3d")
+        ver = (w._version, w.data_ptr(), None if b is None else (b._version, b.data_ptr()))
+        hit = self.cache.get(key)
+        if hit is None or hit[0] != ver:
+            img = spconv.pack_weight(w.detach().permute(0, 2, 3, 4, 1).contiguous(), self.lp) if sub else conv3d.pack_weight(w, self.lp)
+            hit = self.cache[key] = (ver, img, self._vec(b))
+        if not sub:
+            return conv3d.conv3(a16, grid, hit[1], cin, cout, bias=hit[2], addend=addend, store=store)
+        nbr = self.full_grid_map(grid, a16.device)
+        if store == "rows":
+            return spconv.conv3(a16, nbr, hit[1], cout, bias=hit[2], addend=addend, cin=cin)
+        B, X, Y, Z = grid
+        y = spconv.conv3(a16, nbr, hit[1], cout, bias=hit[2], cin=cin).reshape(B, X, Y, Z, cout // 8, 2, 2, 2)
+        y = y.permute(0, 1, 5, 2, 6, 3, 7, 4).reshape(8 * B * X * Y * Z, cout // 8)
+        return y if addend is None else y + addend
+
+    @staticmethod
+    def spconv_route(rows, cin, cout):
+        """Whether gvf_spconv3 takes this dense convolution: its workgroups (64 rows x 64, 128 or 256 channels) number at least 256."""
+        if cin % 64 or cout % 64 or cin > spconv.C_MAX or cout > spconv.C_MAX:
+            return False
+        tile = 256 if cout % 256 == 0 else (128 if cout % 128 == 0 else 64)
+        return (rows + 63) // 64 * (cout // tile) >= 256
+
+    def full_grid_map(self, grid, device):
+        """The neighbour map of the full (B, X, Y, Z) grid in row order, built once per grid and device."""
+        key = ("full_grid_map", tuple(grid), str(device))
+        hit = self.cache.get(key)
+        if hit is None:
+            B, X, Y, Z = grid
+            ax = [torch.arange(n, dtype=torch.int32, device=device) for n in (B, X, Y, Z)]
+            hit = self.cache[key] = spconv.build_neighbor_map(torch.stack(torch.meshgrid(*ax, indexing="ij"), dim=-1).reshape(-1, 4).contiguous())
+        return hit
+
+    @staticmethod
+    def occupancy(logits, grid):
+        """fp32 logits of the dense grid in row order -> int32 (n, 4) coordinates of the cells > 0, row order."""
+        return conv3d.occupancy_coords(logits, grid)
+
     def attention(self, q, k, v, cu_q, cu_k, max_q, max_k, heads, gq=None, gk=None):
         """q (Tq, C), k, v (Tk, C): 16-bit row views with heads packed along C -> (Tq, C)."""
         C = q.shape[1]
@@ -118,14 +168,14 @@ def _slices(st: sp.SparseTensor):
     return [sl for sl in st.layout if sl.stop > sl.start]
 
 
-def _modulated_ln(ops, x, st, eps, shift, scale, act=ACT_NONE):
-    """LayerNorm with one (shift, scale) row per sample: per sample slice."""
+def _modulated_ln(ops, x, layout, eps, shift, scale, act=ACT_NONE):
+    """LayerNorm with one (shift, scale) row per sample: per sample slice (layout: the samples' row slices)."""
     out = None
-    for b, sl in enumerate(st.layout):
+    for b, sl in enumerate(layout):
         if sl.stop == sl.start:
             continue
         part = ops.ln(x[sl], eps, None, None, shift[b], scale[b], act)
-        if len(st.layout) == 1:
+        if len(layout) == 1:
             return part
         if out is None:
             out = torch.empty((x.shape[0], part.shape[1]), dtype=part.dtype, device=part.device)
@@ -168,7 +218,7 @@ class SparseResBlock3d(nn.Module):
         h = ops.conv3(h16, nbr, self.conv1)
         if taps is not None:
             taps.append(h)
-        h16 = _modulated_ln(ops, h, st, self.norm2.eps, shift, scale, ACT_SILU)
+        h16 = _modulated_ln(ops, h, st.layout, self.norm2.eps, shift, scale, ACT_SILU)
         skip = x if isinstance(self.skip_connection, nn.Identity) else ops.linear(ops.cast(x), self.skip_connection, "f32")
         return st, ops.conv3(h16, nbr, self.conv2, addend=skip)
 
@@ -226,15 +276,21 @@ class ModulatedSparseTransformerCrossBlock(nn.Module):
 
     def forward_rows(self, x: torch.Tensor, st: sp.SparseTensor, emb_silu: torch.Tensor, cond: torch.Tensor, ops, taps=None):
         """x: fp32 (T, C) residual rows of `st`, updated in place and returned."""
+        _, _, cu, longest = token_partition(st, "full", None, None, None, None)
+        return self.forward_seqs(x, st.layout, cu, longest, emb_silu, cond, ops, taps)
+
+    def forward_seqs(self, x: torch.Tensor, seqs: List[slice], cu: torch.Tensor, longest: int, emb_silu: torch.Tensor, cond: torch.Tensor, ops,
+                     taps=None):
+        """x: fp32 (T, C) residual rows, sample b's sequence the rows seqs[b]; cu: int32 cu_seqlens of the non-empty sequences, longest: the
+        longest of them.  Updated in place and returned.  The dense flow model calls this with equal-length sequences."""
         C, H = self.channels, self.num_heads
         mod = ops.modulation(emb_silu, self.adaLN_modulation[1])                # (B, 6 C): shift, scale, gate of the attention, of the MLP
         m = [mod[:, i * C:(i + 1) * C] for i in range(6)]
-        _, _, cu, longest = token_partition(st, "full", None, None, None, None)
         sa, ca = self.self_attn, self.cross_attn
         gains = lambda a: (a.q_rms_norm.gamma, a.k_rms_norm.gamma) if a.qk_rms_norm else (None, None)
-        layout = [(b, sl) for b, sl in enumerate(st.layout) if sl.stop > sl.start]
+        layout = [(b, sl) for b, sl in enumerate(seqs) if sl.stop > sl.start]
 
-        hb = _modulated_ln(ops, x, st, self.norm1.eps, m[0], m[1])
+        hb = _modulated_ln(ops, x, seqs, self.norm1.eps, m[0], m[1])
         qkv = ops.linear(hb, sa.to_qkv, "lp")
         ao = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], cu, cu, longest, longest, H, *gains(sa))
         for b, sl in layout:
@@ -250,7 +306,7 @@ class ModulatedSparseTransformerCrossBlock(nn.Module):
         if taps is not None:
             taps.append(x.clone())
 
-        hb = _modulated_ln(ops, x, st, self.norm3.eps, m[3], m[4])
+        hb = _modulated_ln(ops, x, seqs, self.norm3.eps, m[3], m[4])
         hid = ops.linear(hb, self.mlp.mlp[0], "gelu")
         for b, sl in layout:
             ops.linear_resid(x[sl], hid[sl], self.mlp.mlp[2], m[5][b])

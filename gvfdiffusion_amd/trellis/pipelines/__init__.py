@@ -1,1 +1,2 @@
-from .samplers import FlowEulerSampler, FlowEulerCfgSampler, FlowEulerGuidanceIntervalSampler, sample_slat  # noqa: F401
+from .samplers import (FlowEulerSampler, FlowEulerCfgSampler, FlowEulerGuidanceIntervalSampler, sample_slat,  # noqa: F401
+                       sample_sparse_structure, tokens_to_gaussians)

@@ -1,6 +1,7 @@
-"""Euler samplers of the rectified-flow models (trellis/pipelines/samplers/flow_euler.py:11-199 with its two guidance mixins) and
-`sample_slat` (trellis/pipelines/trellis_image_to_3d.py:238-253): noise on the sparse structure's coordinates -> the de-normalised
-structured latent.  Same `sample(...)` arguments and returned fields (`samples`, `pred_x_t`, `pred_x_0`); the state is a SparseTensor or a
+"""Euler samplers of the rectified-flow models (trellis/pipelines/samplers/flow_euler.py:11-199 with its two guidance mixins),
+`sample_sparse_structure` (trellis/pipelines/trellis_image_to_3d.py:165-196): noise on the dense latent grid -> the coordinates of the
+occupied cells, `sample_slat` (:238-253): noise on those coordinates -> the de-normalised structured latent, and `tokens_to_gaussians`,
+which chains the two with the structured-latent Gaussian decoder.  Same `sample(...)` arguments and returned fields (`samples`, `pred_x_t`, `pred_x_0`); the state is a SparseTensor or a
 dense tensor -- only `+`, `-` and scalar `*` are used on it -- and the result is an attrdict in place of easydict.
 
 The flow:  x_t = (1 - t) x_0 + (sigma_min + (1 - sigma_min) t) eps,  the model predicts v = d x_t / d t = (1 - sigma_min) eps - x_0,
@@ -15,7 +16,8 @@ import torch
 from ... import sparse as sp
 from ...attrdict import AttrDict
 
-__all__ = ["FlowEulerSampler", "FlowEulerCfgSampler", "FlowEulerGuidanceIntervalSampler", "sample_slat"]
+__all__ = ["FlowEulerSampler", "FlowEulerCfgSampler", "FlowEulerGuidanceIntervalSampler", "sample_slat", "sample_sparse_structure",
+           "tokens_to_gaussians"]
 
 
 class FlowEulerSampler:
@@ -117,3 +119,44 @@ def sample_slat(flow_model, cond: torch.Tensor, neg_cond: torch.Tensor, coords: 
         mean = torch.tensor(normalization["mean"], dtype=slat.feats.dtype)[None].to(device)
         slat = slat * std + mean
     return slat
+
+
+@torch.no_grad()
+def sample_sparse_structure(flow_model, decoder, cond: torch.Tensor, neg_cond: torch.Tensor, num_samples: int = 1,
+                            sampler_params: Optional[dict] = None, noise: Optional[torch.Tensor] = None, sampler=None,
+                            **model_kwargs) -> torch.Tensor:
+    """The image-condition tokens -> int32 coords (n, 4) = (b, x, y, z) of the sparse structure, on the device and in row order: a guided
+    Euler run of SparseStructureFlowModel over the dense latent, SparseStructureDecoder on its rows, and the cells whose logit is > 0 --
+    torch.argwhere(decoder(z_s) > 0)[:, [0, 2, 3, 4]].  sampler_params: steps, cfg_strength, cfg_interval, rescale_t of
+    FlowEulerGuidanceIntervalSampler (sigma_min 1e-5, the released pipeline's); noise: (num_samples, in_channels, R, R, R), default drawn
+    here as the reference draws it.  model_kwargs (`ops=`) go to both models."""
+    from ..models.sparse_structure_vae import to_rows
+    from ..models.structured_latent_flow import HipOps
+    device = cond.device
+    R = flow_model.resolution
+    if noise is None:
+        noise = torch.randn(num_samples, flow_model.in_channels, R, R, R).to(device)
+    sampler = FlowEulerGuidanceIntervalSampler(sigma_min=1e-5) if sampler is None else sampler
+    z_s = sampler.sample(flow_model, noise.to(device), cond=cond, neg_cond=neg_cond, verbose=False, **(sampler_params or {}), **model_kwargs).samples
+    ops = model_kwargs.get("ops")
+    B = z_s.shape[0]
+    logits, grid = decoder.forward_rows(to_rows(z_s).float(), (B, R, R, R), ops)
+    if logits.shape[1] != 1:
+        raise ValueError(f"the sparse structure is read from ONE occupancy logit per cell, the decoder has {logits.shape[1]} output channels")
+    occupancy = HipOps.occupancy if ops is None else ops.occupancy
+    return occupancy(logits.reshape(B, -1).contiguous(), grid)
+
+
+@torch.no_grad()
+def tokens_to_gaussians(models: dict, cond: torch.Tensor, neg_cond: torch.Tensor, num_samples: int = 1,
+                        sparse_structure_sampler_params: Optional[dict] = None, slat_sampler_params: Optional[dict] = None,
+                        slat_normalization: Optional[dict] = None, noise: Optional[torch.Tensor] = None, **model_kwargs):
+    """The TRELLIS half from the DINOv2 tokens on: sample_sparse_structure -> sample_slat -> SLatGaussianDecoder.  models: the reference
+    pipeline's names -- "sparse_structure_flow_model", "sparse_structure_decoder", "slat_flow_model", "slat_decoder_gs".  -> (the decoder's
+    Gaussians, the structured latent, the coords).  noise: the sparse-structure stage's, default drawn there."""
+    coords = sample_sparse_structure(models["sparse_structure_flow_model"], models["sparse_structure_decoder"], cond, neg_cond, num_samples,
+                                     sparse_structure_sampler_params, noise=noise, **model_kwargs)
+    if coords.shape[0] == 0:
+        raise ValueError("the sparse structure is empty: no cell of the decoder's grid has a positive occupancy logit")
+    slat = sample_slat(models["slat_flow_model"], cond, neg_cond, coords, slat_sampler_params, slat_normalization, **model_kwargs)
+    return models["slat_decoder_gs"](slat), slat, coords
