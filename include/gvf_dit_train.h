@@ -9,9 +9,12 @@
  * row is row / rows_per_group; per-group vectors (scale, gate) are rows of a [G, ld] fp32 table read in place, G = ceil(rows / rows_per_group).
  *
  * Sums over rows: every workgroup owns GVF_TRAIN_ROWS_PER_WG consecutive rows and writes its fp32 partial column sums into the
- * caller's workspace (one slot per workgroup, and one more per group boundary inside its rows -- rows_per_group need not divide
- * anything); ONE further small launch adds the slots of each output in ascending order.  No float atomics: two calls on the same inputs give
- * the same bits, on any stream.
+ * caller's workspace: workgroup wg writes one slot per group g it touches, at index wg + g (rows_per_group need not divide anything), so
+ * group g owns the consecutive slots first_row(g) / 16 + g .. last_row(g) / 16 + g.  That is one slot written per workgroup and one more per
+ * group boundary strictly inside a workgroup's rows; a boundary that falls between two workgroups leaves the index in between unused (never
+ * written, never read), and the *_workspace_bytes queries reserve W + G slots per per-group output (W workgroups, G groups), W per output
+ * that is not per group.  ONE further small launch adds the slots of each output in ascending order.  No float atomics: two calls on the
+ * same inputs give the same bits, on any stream.
  *
  * Two code paths, as gvf_layernorm_modulate: C % 256 == 0 && C <= 1024 keeps the row in registers and moves it with 8- / 16-byte accesses (then
  * fp32 rows, ln_w, ln_b, the table rows (ld % 4 == 0) must be 16-byte aligned and 16-bit rows 8-byte aligned); any other C takes a generic path
