@@ -9,6 +9,7 @@
 #include <cmath>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_dit_train.h"
@@ -17,31 +18,14 @@ namespace {
 
 constexpr int RPW = GVF_TRAIN_ROWS_PER_WG;        // rows per workgroup (4 waves, rows r0 + wave + 4 i)
 
-// Sum over the 64 lanes, every lane gets it (elem.hip's wave_sum: DPP / permlane paths only)
-#define GVF_DPP(x_, ctrl_) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x_), ctrl_, 0xF, 0xF, false))
-__device__ __forceinline__ float wave_sum(float v) {
-    v += GVF_DPP(v, 0xB1);      // quad_perm [1,0,3,2]: lane ^ 1
-    v += GVF_DPP(v, 0x4E);      // quad_perm [2,3,0,1]: lane ^ 2
-    v += GVF_DPP(v, 0x141);     // row_half_mirror
-    v += GVF_DPP(v, 0x140);     // row_mirror
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned a0 = r16[0], a1 = r16[1];
-    const float w = __uint_as_float(a0) + __uint_as_float(a1);
-    const unsigned uw = __builtin_bit_cast(unsigned, w);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);
-    const unsigned b0 = r32[0], b1 = r32[1];
-    return __uint_as_float(b0) + __uint_as_float(b1);
-}
-// Sum over aligned groups of NL = 4 or 8 lanes (one head of the RMSNorm: 8 channels per lane)
+// Sum over aligned groups of NL = 4 or 8 lanes (one head of the RMSNorm: 8 channels per lane): the first steps of gvf_wave_sum_dpp
 template <int NL>
 __device__ __forceinline__ float group_sum(float v) {
-    v += GVF_DPP(v, 0xB1);
-    v += GVF_DPP(v, 0x4E);
-    if (NL == 8) v += GVF_DPP(v, 0x141);
+    v += GVF_ROWOPS_DPP_F32(v, 0xB1);
+    v += GVF_ROWOPS_DPP_F32(v, 0x4E);
+    if (NL == 8) v += GVF_ROWOPS_DPP_F32(v, 0x141);
     return v;
 }
-#undef GVF_DPP
 
 // The slot of workgroup wg's partial for group g: wg + g.  A workgroup's rows cover groups g_lo..g_hi and the next workgroup starts at a
 // group >= g_hi, so the pairs (wg, g) in row order get strictly increasing slots, and the slots of one group are consecutive:
@@ -116,18 +100,18 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
             // mean as a two-term sum mean + mean_lo: with one fp32 term a row whose mean is 100 x its spread (a residual stream with a common
             // offset) carries half an ulp of the MEAN into every centred value, 1e-5 of xh -- invisible in the 16-bit forward output, the
             // largest error of the fp32 gradients
-            const float mean = wave_sum(s) / (float)C;
+            const float mean = gvf_wave_sum_dpp(s) / (float)C;
             float r = 0.f;
 #pragma unroll
             for (int i = 0; i < VPL; ++i) r += ((v[i].x - mean) + (v[i].y - mean)) + ((v[i].z - mean) + (v[i].w - mean));
-            const float mean_lo = wave_sum(r) / (float)C;
+            const float mean_lo = gvf_wave_sum_dpp(r) / (float)C;
             float q = 0.f;
 #pragma unroll
             for (int i = 0; i < VPL; ++i) {
                 v[i].x = (v[i].x - mean) - mean_lo; v[i].y = (v[i].y - mean) - mean_lo; v[i].z = (v[i].z - mean) - mean_lo; v[i].w = (v[i].w - mean) - mean_lo;
                 q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
             }
-            const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+            const float rstd = rsqrtf(gvf_wave_sum_dpp(q) / (float)C + eps);
             float xh[VPL][4], gg[VPL][4];
             float sg = 0.f, sgx = 0.f;
 #pragma unroll
@@ -148,7 +132,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
                     sgx += gg[i][e] * xh[i][e];
                 }
             }
-            const float c1 = wave_sum(sg) / (float)C, c2 = wave_sum(sgx) / (float)C;
+            const float c1 = gvf_wave_sum_dpp(sg) / (float)C, c2 = gvf_wave_sum_dpp(sgx) / (float)C;
             float4* dxr = reinterpret_cast<float4*>(dx + (size_t)row * C);
             const float4* rr = reinterpret_cast<const float4*>(dres + (size_t)row * C);
 #pragma unroll
@@ -190,13 +174,13 @@ __global__ __launch_bounds__(256) void ln_bwd_generic_kernel(const float* __rest
         const unsigned short* dr = dy + (size_t)row * C;
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s += xr[c];
-        const float mean = wave_sum(s) / (float)C;
+        const float mean = gvf_wave_sum_dpp(s) / (float)C;
         float r = 0.f;
         for (int c = lane; c < C; c += 64) r += xr[c] - mean;
-        const float mean_lo = wave_sum(r) / (float)C;           // (the two-term mean of ln_bwd_kernel)
+        const float mean_lo = gvf_wave_sum_dpp(r) / (float)C;           // (the two-term mean of ln_bwd_kernel)
         float q = 0.f;
         for (int c = lane; c < C; c += 64) { const float a = (xr[c] - mean) - mean_lo; q += a * a; }
-        const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+        const float rstd = rsqrtf(gvf_wave_sum_dpp(q) / (float)C + eps);
         const float* sc = scale != nullptr ? scale + (size_t)(row / rpg) * mod_ld : nullptr;
         float sg = 0.f, sgx = 0.f;
         for (int c = lane; c < C; c += 64) {
@@ -207,7 +191,7 @@ __global__ __launch_bounds__(256) void ln_bwd_generic_kernel(const float* __rest
             sg += g;
             sgx += g * xh;
         }
-        const float c1 = wave_sum(sg) / (float)C, c2 = wave_sum(sgx) / (float)C;
+        const float c1 = gvf_wave_sum_dpp(sg) / (float)C, c2 = gvf_wave_sum_dpp(sgx) / (float)C;
         for (int c = lane; c < C; c += 64) {
             const float xh = ((xr[c] - mean) - mean_lo) * rstd;
             float g = GvfLp<DT>::from16(dr[c]);
@@ -350,17 +334,6 @@ __global__ __launch_bounds__(256) void gate_bwd_generic_kernel(const float* __re
 // ---- c. multi-head RMSNorm --------------------------------------------------------------------------------------------------------------
 // A lane holds 8 consecutive channels (16 bytes), D / 8 lanes a head, a wave 512 channels per trip; HD = H * D is a multiple of 32, so a
 // lane's 8 channels are all inside the row or all outside.
-template <int DT>
-__device__ __forceinline__ void unpack8(uint4 q, float (&f)[8]) {
-    f[0] = GvfLp<DT>::lo(q.x); f[1] = GvfLp<DT>::hi(q.x); f[2] = GvfLp<DT>::lo(q.y); f[3] = GvfLp<DT>::hi(q.y);
-    f[4] = GvfLp<DT>::lo(q.z); f[5] = GvfLp<DT>::hi(q.z); f[6] = GvfLp<DT>::lo(q.w); f[7] = GvfLp<DT>::hi(q.w);
-}
-template <int DT>
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    uint4 q;
-    q.x = GvfLp<DT>::pack(f[0], f[1]); q.y = GvfLp<DT>::pack(f[2], f[3]); q.z = GvfLp<DT>::pack(f[4], f[5]); q.w = GvfLp<DT>::pack(f[6], f[7]);
-    return q;
-}
 __device__ __forceinline__ void load8(const float* p, float (&f)[8]) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
@@ -380,7 +353,7 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const unsigned short* __re
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = gm[e] = 0.f;
         if (on) {
-            unpack8<DT>(*reinterpret_cast<const uint4*>(x + (size_t)row * ldx + c0), f);
+            gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(x + (size_t)row * ldx + c0), f);
             load8(gamma + c0, gm);
         }
         float ss = 0.f;
@@ -390,7 +363,7 @@ __global__ __launch_bounds__(256) void rms_fwd_kernel(const unsigned short* __re
         float o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = ((f[e] / den) * gm[e]) * sqrt_d;
-        if (on) *reinterpret_cast<uint4*>(y + (size_t)row * ldy + c0) = pack8<DT>(o);
+        if (on) *reinterpret_cast<uint4*>(y + (size_t)row * ldy + c0) = gvf_pack8<DT>(o);
     }
 }
 
@@ -420,8 +393,8 @@ __global__ __launch_bounds__(256) void rms_bwd_kernel(const unsigned short* __re
 #pragma unroll
             for (int e = 0; e < 8; ++e) f[e] = d[e] = 0.f;
             if (on) {
-                unpack8<DT>(*reinterpret_cast<const uint4*>(x + (size_t)row * ldx + c0), f);
-                unpack8<DT>(*reinterpret_cast<const uint4*>(dy + (size_t)row * lddy + c0), d);
+                gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(x + (size_t)row * ldx + c0), f);
+                gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(dy + (size_t)row * lddy + c0), d);
             }
             float ss = 0.f;
 #pragma unroll
@@ -439,7 +412,7 @@ __global__ __launch_bounds__(256) void rms_bwd_kernel(const unsigned short* __re
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (u[e] - xt[e] * dot) / den;
-            if (on) *reinterpret_cast<uint4*>(dx + (size_t)row * lddx + c0) = pack8<DT>(o);
+            if (on) *reinterpret_cast<uint4*>(dx + (size_t)row * lddx + c0) = gvf_pack8<DT>(o);
         }
     }
     // the four waves' partials -> slot blockIdx.x (waves in order); lds: 4 * HD floats
@@ -483,8 +456,6 @@ __global__ __launch_bounds__(256) void colsum_finalize_kernel(ColsumJobs jobs, i
 
 inline long long n_wg(long long rows) { return (rows + RPW - 1) / RPW; }
 inline long long n_groups(long long rows, long long rpg) { return (rows + rpg - 1) / rpg; }
-inline bool lp_ok(int dtype) { return dtype == GVF_DT_BF16 || dtype == GVF_DT_F16; }
-inline bool mis(const void* p, uintptr_t mask) { return (((uintptr_t)p) & mask) != 0; }
 inline bool vec_path(int C) { return (C % 256) == 0 && C <= 1024; }
 
 int launch_finalize(const ColsumJobs& jobs, int n_jobs, long long max_G, int n_cols, long long rows, hipStream_t stream) {
@@ -507,7 +478,7 @@ extern "C" int gvf_ln_mod_bwd_workspace_bytes(int rows, int C, int rows_per_grou
 extern "C" int gvf_ln_mod_bwd(int dtype, const float* x, const void* dy, const float* dres, float* dx, int rows, int C, float eps,
                               const float* ln_w, const float* ln_b, const float* scale, int mod_ld, int rows_per_group,
                               float* dshift, float* dscale, float* dw, float* db, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!lp_ok(dtype)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype)) return GVF_EINVAL;
     if (rows < 0 || C <= 0) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
     if (!x || !dy || !dx) return GVF_EINVAL;
@@ -515,13 +486,13 @@ extern "C" int gvf_ln_mod_bwd(int dtype, const float* x, const void* dy, const f
     if ((dshift == nullptr) != (scale == nullptr) || (dscale == nullptr) != (scale == nullptr)) return GVF_EINVAL;
     if (scale != nullptr && (rows_per_group <= 0 || mod_ld < C)) return GVF_EINVAL;
     const bool vec = vec_path(C);
-    if (vec && (mis(x, 15) || mis(dx, 15) || mis(dres, 15) || mis(dy, 7) || mis(ln_w, 15) || mis(ln_b, 15) || mis(scale, 15) ||
+    if (vec && (gvf_mis(x, 15) || gvf_mis(dx, 15) || gvf_mis(dres, 15) || gvf_mis(dy, 7) || gvf_mis(ln_w, 15) || gvf_mis(ln_b, 15) || gvf_mis(scale, 15) ||
                 (scale != nullptr && (mod_ld % 4) != 0)))
         return GVF_EINVAL;
     const bool sums = scale != nullptr || ln_w != nullptr;
     size_t need = 0;
     if (gvf_ln_mod_bwd_workspace_bytes(rows, C, scale != nullptr ? rows_per_group : 0, &need) != GVF_OK) return GVF_EINVAL;
-    if (sums && (!workspace || workspace_bytes < need || mis(workspace, 15))) return GVF_EINVAL;
+    if (sums && (!workspace || workspace_bytes < need || gvf_mis(workspace, 15))) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     const long long rpg = scale != nullptr ? rows_per_group : rows;
@@ -562,13 +533,13 @@ extern "C" int gvf_ln_mod_bwd(int dtype, const float* x, const void* dy, const f
 
 extern "C" int gvf_gate_residual_fwd(int dtype, const float* x, const void* h, const float* gate, int gate_ld, int rows_per_group, float* out,
                                      int rows, int C, void* stream_) {
-    if (!lp_ok(dtype)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype)) return GVF_EINVAL;
     if (rows < 0 || C <= 0) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
     if (!x || !h || !out) return GVF_EINVAL;
     if (gate != nullptr && (rows_per_group <= 0 || gate_ld < C)) return GVF_EINVAL;
     const bool vec = vec_path(C);
-    if (vec && (mis(x, 15) || mis(out, 15) || mis(h, 7) || mis(gate, 15) || (gate != nullptr && (gate_ld % 4) != 0))) return GVF_EINVAL;
+    if (vec && (gvf_mis(x, 15) || gvf_mis(out, 15) || gvf_mis(h, 7) || gvf_mis(gate, 15) || (gate != nullptr && (gate_ld % 4) != 0))) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     const long long rpg = gate != nullptr ? rows_per_group : rows;
@@ -599,17 +570,17 @@ extern "C" int gvf_gate_residual_bwd_workspace_bytes(int rows, int C, int rows_p
 
 extern "C" int gvf_gate_residual_bwd(int dtype, const float* dout, const void* h, const float* gate, int gate_ld, int rows_per_group, void* dh,
                                      float* dgate, int rows, int C, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!lp_ok(dtype)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype)) return GVF_EINVAL;
     if (rows < 0 || C <= 0) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
     if (!dout || !dh) return GVF_EINVAL;
     if ((dgate == nullptr) != (gate == nullptr)) return GVF_EINVAL;
     if (gate != nullptr && (!h || rows_per_group <= 0 || gate_ld < C)) return GVF_EINVAL;
     const bool vec = vec_path(C);
-    if (vec && (mis(dout, 15) || mis(dh, 7) || mis(h, 7) || mis(gate, 15) || (gate != nullptr && (gate_ld % 4) != 0))) return GVF_EINVAL;
+    if (vec && (gvf_mis(dout, 15) || gvf_mis(dh, 7) || gvf_mis(h, 7) || gvf_mis(gate, 15) || (gate != nullptr && (gate_ld % 4) != 0))) return GVF_EINVAL;
     size_t need = 0;
     if (gvf_gate_residual_bwd_workspace_bytes(rows, C, gate != nullptr ? rows_per_group : 0, &need) != GVF_OK) return GVF_EINVAL;
-    if (gate != nullptr && (!workspace || workspace_bytes < need || mis(workspace, 15))) return GVF_EINVAL;
+    if (gate != nullptr && (!workspace || workspace_bytes < need || gvf_mis(workspace, 15))) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     const long long rpg = gate != nullptr ? rows_per_group : rows;
@@ -638,7 +609,7 @@ extern "C" int gvf_gate_residual_bwd(int dtype, const float* dout, const void* h
 }
 
 static int rms_args_ok(int dtype, int rows, int H, int d) {
-    if (!lp_ok(dtype)) return 0;
+    if (!gvf_lp_ok(dtype)) return 0;
     if (rows < 0 || H <= 0 || (d != 32 && d != 64)) return 0;
     if ((long long)H * d > 2048) return 0;
     return 1;
@@ -650,7 +621,7 @@ extern "C" int gvf_rmsnorm_heads_fwd(int dtype, const void* x, int64_t ldx, cons
     if (rows == 0) return GVF_OK;
     const int HD = H * d;
     if (!x || !gamma || !y) return GVF_EINVAL;
-    if (ldx < HD || ldy < HD || (ldx % 8) != 0 || (ldy % 8) != 0 || mis(x, 15) || mis(y, 15) || mis(gamma, 15)) return GVF_EINVAL;
+    if (ldx < HD || ldy < HD || (ldx % 8) != 0 || (ldy % 8) != 0 || gvf_mis(x, 15) || gvf_mis(y, 15) || gvf_mis(gamma, 15)) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     const dim3 grid((unsigned)((rows + 3) / 4)), block(256);
@@ -675,8 +646,8 @@ extern "C" int gvf_rmsnorm_heads_bwd(int dtype, const void* x, int64_t ldx, cons
     if (rows == 0) return GVF_OK;
     const int HD = H * d;
     if (!x || !dy || !gamma || !dx || !dgamma || !workspace) return GVF_EINVAL;
-    if (ldx < HD || lddy < HD || lddx < HD || (ldx % 8) != 0 || (lddy % 8) != 0 || (lddx % 8) != 0 || mis(x, 15) || mis(dy, 15) || mis(dx, 15) ||
-        mis(gamma, 15) || mis(workspace, 15))
+    if (ldx < HD || lddy < HD || lddx < HD || (ldx % 8) != 0 || (lddy % 8) != 0 || (lddx % 8) != 0 || gvf_mis(x, 15) || gvf_mis(dy, 15) || gvf_mis(dx, 15) ||
+        gvf_mis(gamma, 15) || gvf_mis(workspace, 15))
         return GVF_EINVAL;
     size_t need = 0;
     if (gvf_rmsnorm_heads_bwd_workspace_bytes(rows, H, d, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;

@@ -8,6 +8,7 @@
 #include <cmath>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 
@@ -18,25 +19,6 @@ __device__ __forceinline__ unsigned short f2bf(float f) {
     if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (unsigned short)(u >> 16);
-}
-
-// Sum over the 64 lanes, every lane gets it -- on the DPP / permlane data paths only (quad_perm, row mirrors, v_permlane16_swap,
-// v_permlane32_swap), nothing through the LDS unit.
-__device__ __forceinline__ float wave_sum(float v) {
-#define GVF_DPP(x_, ctrl_) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x_), ctrl_, 0xF, 0xF, false))
-    v += GVF_DPP(v, 0xB1);      // quad_perm [1,0,3,2]: lane ^ 1
-    v += GVF_DPP(v, 0x4E);      // quad_perm [2,3,0,1]: lane ^ 2
-    v += GVF_DPP(v, 0x141);     // row_half_mirror: lane i of 8 <-> 7 - i (the other quad of the half row)
-    v += GVF_DPP(v, 0x140);     // row_mirror: lane i of 16 <-> 15 - i (the other half of the row)
-#undef GVF_DPP
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);      // {rows 0,0,2,2 | rows 1,1,3,3}: their sum = rows 0+1 | 2+3
-    const unsigned a0 = r16[0], a1 = r16[1];
-    const float w = __uint_as_float(a0) + __uint_as_float(a1);
-    const unsigned uw = __builtin_bit_cast(unsigned, w);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);
-    const unsigned b0 = r32[0], b1 = r32[1];
-    return __uint_as_float(b0) + __uint_as_float(b1);
 }
 
 // VPL = float4 loads per lane: C = 64 * 4 * VPL
@@ -56,14 +38,14 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const float* __restrict__ x
         v[i] = xr[lane + 64 * i];
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(s) / (float)C;
+    const float mean = gvf_wave_sum_dpp(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
         q += (a * a + b * b) + (c * c + d * d);
     }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    const float rstd = rsqrtf(gvf_wave_sum_dpp(q) / (float)C + eps);
     const int g = row / rpg;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -99,10 +81,10 @@ __global__ __launch_bounds__(256) void ln_mod_generic_kernel(const float* __rest
     const float* xr = x + (size_t)row * C;
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += xr[c];
-    const float mean = wave_sum(s) / (float)C;
+    const float mean = gvf_wave_sum_dpp(s) / (float)C;
     float q = 0.f;
     for (int c = lane; c < C; c += 64) { const float a = xr[c] - mean; q += a * a; }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    const float rstd = rsqrtf(gvf_wave_sum_dpp(q) / (float)C + eps);
     const int g = row / rpg;
     for (int c = lane; c < C; c += 64) {
         float y = (xr[c] - mean) * rstd;
@@ -201,7 +183,7 @@ __device__ __forceinline__ void te_dot8(const unsigned short* __restrict__ W, in
                       (__uint_as_float(w[u].y << 16) * x.z + __uint_as_float(w[u].y & 0xffff0000u) * x.w);
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] = wave_sum(acc[u]);
+    for (int u = 0; u < 8; ++u) acc[u] = gvf_wave_sum_dpp(acc[u]);
 }
 
 __global__ __launch_bounds__(1024) void timestep_embed_kernel(const float* __restrict__ t, int F, float neg_log_period,
@@ -276,7 +258,7 @@ __device__ __forceinline__ void dot8_f32(const float* __restrict__ W, int ldw, i
         for (int u = 0; u < 8; ++u) acc[u] += (w[u].x * x.x + w[u].y * x.y) + (w[u].z * x.z + w[u].w * x.w);
     }
 #pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] = wave_sum(acc[u]);
+    for (int u = 0; u < 8; ++u) acc[u] = gvf_wave_sum_dpp(acc[u]);
 }
 
 // TimestepEmbedder in fp32: out[b] = silu(W2 silu(W0 [cos | sin](t_b f) + b0) + b2) (the input of every adaLN projection), t_emb optional
@@ -425,10 +407,10 @@ __global__ __launch_bounds__(256) void final_layer_f32_kernel(const float* __res
             const float4* xn = reinterpret_cast<const float4*>(x + (size_t)(row + stride) * C);
             nxt0 = xn[i0]; nxt1 = xn[i1];
         }
-        const float mean = wave_sum((v0.x + v0.y) + (v0.z + v0.w) + (v1.x + v1.y) + (v1.z + v1.w)) / (float)C;
+        const float mean = gvf_wave_sum_dpp((v0.x + v0.y) + (v0.z + v0.w) + (v1.x + v1.y) + (v1.z + v1.w)) / (float)C;
         if (ok0) { v0.x -= mean; v0.y -= mean; v0.z -= mean; v0.w -= mean; }
         if (ok1) { v1.x -= mean; v1.y -= mean; v1.z -= mean; v1.w -= mean; }
-        const float rstd = rsqrtf(wave_sum((v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w) + (v1.x * v1.x + v1.y * v1.y) + (v1.z * v1.z + v1.w * v1.w)) / (float)C + eps);
+        const float rstd = rsqrtf(gvf_wave_sum_dpp((v0.x * v0.x + v0.y * v0.y) + (v0.z * v0.z + v0.w * v0.w) + (v1.x * v1.x + v1.y * v1.y) + (v1.z * v1.z + v1.w * v1.w)) / (float)C + eps);
         float4 sc0 = z4, sh0 = z4, sc1 = z4, sh1 = z4;
         if (scale != nullptr) {
             const size_t mo = (size_t)(rpg > 0 ? row / rpg : 0) * mod_ld;

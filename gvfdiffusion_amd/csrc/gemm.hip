@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 
@@ -35,8 +36,6 @@ __device__ __forceinline__ float gelu_tanh(float x) {
     const float u = k0 * (x + k1 * x * x * x);
     return x / (1.0f + __expf(-2.0f * u));
 }
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }   // as csrc/vae.hip's geglu kernel
 
 // LDS-DMA of one 16-byte chunk per lane.  Kept out of the kernel template on purpose: with template-dependent
 // arguments clang checks the builtin only at instantiation, where the HOST pass rejects it silently and then emits
@@ -295,7 +294,7 @@ __global__ __launch_bounds__(THREADS, BN == 192 ? 3 : (BK == 32 ? 4 : (BM == 64 
                 const float g4[4] = {vg.x + bg.x, vg.y + bg.y, vg.z + bg.z, vg.w + bg.w};
                 float o4[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o4[e] = LP::from16(LP::to16(a4[e])) * gelu_erf(LP::from16(LP::to16(g4[e])));
+                for (int e = 0; e < 4; ++e) o4[e] = LP::from16(LP::to16(a4[e])) * gvf_gelu_erf(LP::from16(LP::to16(g4[e])));
                 uint2 w2;
                 w2.x = LP::pack(o4[0], o4[1]); w2.y = LP::pack(o4[2], o4[3]);
                 *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(Cv) + (size_t)row * ldc + ((bn + wn * (BN / 2) + cg * 64) >> 1) + ec) = w2;

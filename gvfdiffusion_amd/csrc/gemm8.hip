@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 
@@ -43,8 +44,6 @@ constexpr int G8_BK = 64;
 __device__ __forceinline__ void g8_dma16(const unsigned short* g, uint4* l) {
     __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
-
-__device__ __forceinline__ float g8_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }   // as csrc/gemm.hip / csrc/vae.hip
 
 template <int DT, int EPI, int T>
 __global__ __launch_bounds__(G8_THREADS, 1) void gemm8_kernel(const unsigned short* __restrict__ A, int lda, const unsigned short* __restrict__ W, int ldw,
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(G8_THREADS, 1) void gemm8_kernel(const unsigned sho
                 float o4[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    o4[r] = LP::from16(LP::to16(acc[i][j][r] + bvv[r])) * g8_gelu_erf(LP::from16(LP::to16(acc[i + 2][j][r] + bgg[r])));
+                    o4[r] = LP::from16(LP::to16(acc[i][j][r] + bvv[r])) * gvf_gelu_erf(LP::from16(LP::to16(acc[i + 2][j][r] + bgg[r])));
                 uint2 w2;
                 w2.x = LP::pack(o4[0], o4[1]); w2.y = LP::pack(o4[2], o4[3]);
                 *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(so) + m * 64 + (((2 * i + (lq >> 1)) ^ ((m >> 1) & 3)) * 16) + 8 * (lq & 1)) = w2;

@@ -14,6 +14,7 @@
 // Every loop is bounded by an argument; no workgroup waits for another.
 // Built with -ffp-contract=off (_build.py): rule 1 rounds every operation on its own (index decisions), rule 4 is a fixed sequence.
 #include "gvf_common.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_interp.h"
 
@@ -129,19 +130,6 @@ __global__ __launch_bounds__(NT) void knn_search_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = GVF_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GVF_WAVE);
-    const int wave = threadIdx.x / GVF_WAVE;
-    if ((threadIdx.x & (GVF_WAVE - 1)) == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < NT / GVF_WAVE; ++i) s += red[i];
-    __syncthreads();
-    return s;   // valid in thread 0
-}
-
 __device__ __forceinline__ int sgn3(double d) { return d > 0.0 ? 2 : (d < 0.0 ? 0 : 1); }   // sign + 1
 
 // grid: (ceil(P / NT), frame chunks, B); frames [blockIdx.y * tc, min(T, (blockIdx.y + 1) * tc)).
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(NT) void interp_apply_kernel(const float* __restric
         }
     }
     if (LOSS) {
-        const double s = block_sum(acc, s_red);
+        const double s = gvf_block_sum_waves<NT>(acc, s_red);
         if (threadIdx.x == 0) part[((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = s;
     }
 }
@@ -230,7 +218,7 @@ __global__ __launch_bounds__(NT) void interp_loss_reduce_kernel(const double* __
     __shared__ double s_red[NT / GVF_WAVE];
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < nblk; i += NT) s += part[i];
-    s = block_sum(s, s_red);
+    s = gvf_block_sum_waves<NT>(s, s_red);
     if (threadIdx.x == 0) loss_out[0] = (float)(s / (3.0 * (double)T * valid_total(len, B, P)));
 }
 

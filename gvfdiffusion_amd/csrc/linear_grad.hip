@@ -15,6 +15,7 @@
 // Split over m and the reduction: see the header.  One k-step = one MFMA per accumulator = one fp32 rounding of the running sum.
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_linear_grad.h"
@@ -195,21 +196,18 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(const float* __rest
     }
 }
 
-inline bool lp_ok(int dtype) { return dtype == GVF_DT_BF16 || dtype == GVF_DT_F16; }
-inline bool mis(const void* p, uintptr_t mask) { return (((uintptr_t)p) & mask) != 0; }
-inline long long ceil_div(long long a, long long b) { return (a + b - 1) / b; }
 
 inline long long slot_floats(int N, int K) { return (long long)N * K + N; }
 
 }  // namespace
 
 extern "C" int gvf_cast_transpose(int dtype, const float* W, int ldw, void* W16, int ld_k, void* W16T, int ld_n, int N, int K, void* stream_) {
-    if (!lp_ok(dtype)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype)) return GVF_EINVAL;
     if (N <= 0 || K <= 0 || ldw < K || ld_k < K || ld_n < N || (ld_k % 8) != 0 || (ld_n % 8) != 0) return GVF_EINVAL;
     if (!W || !W16 || !W16T) return GVF_EINVAL;
-    if (mis(W, 3) || mis(W16, 3) || mis(W16T, 3)) return GVF_EINVAL;
+    if (gvf_mis(W, 3) || gvf_mis(W16, 3) || gvf_mis(W16T, 3)) return GVF_EINVAL;
     (void)hipGetLastError();
-    const dim3 grid((unsigned)ceil_div(ld_k, 64), (unsigned)ceil_div(ld_n, 64));
+    const dim3 grid((unsigned)gvf_cdiv(ld_k, 64), (unsigned)gvf_cdiv(ld_n, 64));
     if (grid.y > 65535u) return GVF_EINVAL;
     GVF_LP_DISPATCH(dtype, hipLaunchKernelGGL(cast_transpose_kernel<DT>, grid, dim3(256), 0, (hipStream_t)stream_, W, (long long)ldw,
                                               (unsigned short*)W16, (long long)ld_k, (unsigned short*)W16T, (long long)ld_n, N, K));
@@ -219,8 +217,8 @@ extern "C" int gvf_cast_transpose(int dtype, const float* W, int ldw, void* W16,
 
 extern "C" int gvf_gemm_wgrad_splits(int M, int N, int K) {
     if (M < 0 || N <= 0 || K <= 0) return GVF_EINVAL;
-    const long long tiles = ceil_div(N, BT) * ceil_div(K, BT);
-    const long long steps = ceil_div(M, KSTEP);
+    const long long tiles = gvf_cdiv(N, BT) * gvf_cdiv(K, BT);
+    const long long steps = gvf_cdiv(M, KSTEP);
     long long s = 2 * WGRAD_CUS / tiles;
     if (s > WGRAD_MAX_AUTO) s = WGRAD_MAX_AUTO;
     if (s > steps / WGRAD_MIN_STEPS) s = steps / WGRAD_MIN_STEPS;
@@ -236,18 +234,18 @@ extern "C" int gvf_gemm_wgrad_workspace_bytes(int M, int N, int K, int splits, s
 
 extern "C" int gvf_gemm_wgrad(int dtype, const void* dY, int ldy, const void* X, int ldx, int M, int N, int K, float* dW, int lddw, float* db,
                               void* workspace, size_t workspace_bytes, int splits, void* stream_) {
-    if (!lp_ok(dtype)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype)) return GVF_EINVAL;
     if (M < 0 || N <= 0 || K <= 0 || (N % 8) != 0 || (K % 8) != 0) return GVF_EINVAL;
     if (ldy < N || ldx < K || lddw < K || (ldy % 8) != 0 || (ldx % 8) != 0 || (lddw % 8) != 0) return GVF_EINVAL;
     if (splits < 0 || splits > WGRAD_MAX_SPLITS) return GVF_EINVAL;
     if (!dY || !X || !dW || !workspace) return GVF_EINVAL;
-    if (mis(dY, 15) || mis(X, 15) || mis(dW, 15) || mis(db, 15) || mis(workspace, 15)) return GVF_EINVAL;
+    if (gvf_mis(dY, 15) || gvf_mis(X, 15) || gvf_mis(dW, 15) || gvf_mis(db, 15) || gvf_mis(workspace, 15)) return GVF_EINVAL;
     if (splits == 0) splits = gvf_gemm_wgrad_splits(M, N, K);
     size_t need = 0;
     if (gvf_gemm_wgrad_workspace_bytes(M, N, K, splits, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;
-    const long long tiles_n = ceil_div(N, BT), tiles_k = ceil_div(K, BT);
+    const long long tiles_n = gvf_cdiv(N, BT), tiles_k = gvf_cdiv(K, BT);
     if (tiles_n > 65535) return GVF_EINVAL;
-    const int steps_per_group = (int)ceil_div(ceil_div(M, KSTEP), splits);
+    const int steps_per_group = (int)gvf_cdiv(gvf_cdiv(M, KSTEP), splits);
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     float* ws = (float*)workspace;
@@ -256,7 +254,7 @@ extern "C" int gvf_gemm_wgrad(int dtype, const void* dY, int ldy, const void* X,
                                               slot_floats(N, K), db != nullptr ? 1 : 0));
     GVF_CHECK_LAUNCH();
     const long long total4 = (slot_floats(N, K) - (db != nullptr ? 0 : N)) / 4;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, stream, ws, slot_floats(N, K), splits, dW, lddw, db, N,
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)gvf_cdiv(total4, 256)), dim3(256), 0, stream, ws, slot_floats(N, K), splits, dW, lddw, db, N,
                        K);
     GVF_CHECK_LAUNCH();
     return GVF_OK;

@@ -11,6 +11,7 @@
 // Built with -ffp-contract=off (_build.py): fmaf only where written, so that identical inputs give identical numerator and
 // denominator terms (S = 1 exactly up to the rounding of the division).
 #include "gvf_common.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_loss.h"
 
@@ -95,19 +96,6 @@ __device__ __forceinline__ void vpass(float (*h)[SH][TW], int r0, int c, float (
     }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = GVF_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GVF_WAVE);
-    const int wave = threadIdx.x / GVF_WAVE;
-    if ((threadIdx.x & (GVF_WAVE - 1)) == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < NT / GVF_WAVE; ++w) s += red[w];
-    __syncthreads();
-    return s;   // valid in thread 0
-}
-
 template <bool GRAD>
 __global__ __launch_bounds__(NT) void image_loss_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int H, int W,
                                                             int tiles_x, int tiles_y, int64_t n, double* __restrict__ part,
@@ -164,8 +152,8 @@ __global__ __launch_bounds__(NT) void image_loss_fwd_kernel(const float* __restr
             maps[2 * n + o] = ds12;
         }
     }
-    const double bs = block_sum((double)ssum, s_red[0]);
-    const double bl = block_sum((double)lsum, s_red[1]);
+    const double bs = gvf_block_sum_waves<NT>((double)ssum, s_red[0]);
+    const double bl = gvf_block_sum_waves<NT>((double)lsum, s_red[1]);
     if (threadIdx.x == 0) {
         part[2 * (int64_t)blockIdx.x] = bs;
         part[2 * (int64_t)blockIdx.x + 1] = bl;
@@ -181,8 +169,8 @@ __global__ __launch_bounds__(NT) void image_loss_reduce_kernel(const double* __r
         s += part[2 * i];
         l += part[2 * i + 1];
     }
-    s = block_sum(s, s_red[0]);
-    l = block_sum(l, s_red[1]);
+    s = gvf_block_sum_waves<NT>(s, s_red[0]);
+    l = gvf_block_sum_waves<NT>(l, s_red[1]);
     if (threadIdx.x == 0) {
         const double ms = s / (double)n, ml = l / (double)n;
         terms[0] = (float)((double)w_l1 * ml + (double)w_ssim * (1.0 - ms));

@@ -9,6 +9,7 @@
 // workgroup per image adds the partials in a fixed order (no float atomics: bit-identical run to run).
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_lpips.h"
@@ -23,12 +24,6 @@ constexpr int TAP_MAX_BLOCKS = 512;     // workgroups per image of the tap kerne
 __device__ __forceinline__ bool positive16(unsigned short h) { return h != 0 && !(h & 0x8000u); }
 
 // ---- pool ------------------------------------------------------------------------------------------------------------------------------
-template <int DT>
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-    typedef GvfLp<DT> L;
-    f[0] = L::lo(v.x); f[1] = L::hi(v.x); f[2] = L::lo(v.y); f[3] = L::hi(v.y);
-    f[4] = L::lo(v.z); f[5] = L::hi(v.z); f[6] = L::lo(v.w); f[7] = L::hi(v.w);
-}
 __device__ __forceinline__ unsigned short half_of(const uint4& v, int e) {
     const unsigned w = e < 2 ? v.x : (e < 4 ? v.y : (e < 6 ? v.z : v.w));
     return (unsigned short)((e & 1) ? (w >> 16) : (w & 0xffffu));
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(NT) void pool_fwd_kernel(const unsigned short* __re
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             v[k] = *(const uint4*)(in + ((n * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + 8 * c8);
-            unpack8<DT>(v[k], f[k]);
+            gvf_unpack8<DT>(v[k], f[k]);
         }
         unsigned short r[8];
 #pragma unroll
@@ -94,7 +89,7 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const unsigned short* __re
         const int64_t o = ((n * H + y) * W + x) * C + 8 * c8;
         const uint4 own = *(const uint4*)(a + o);
         float t[8], g[8];
-        unpack8<0>(*(const uint4*)(tg + o), t);
+        gvf_unpack8<0>(*(const uint4*)(tg + o), t);
         bool mine[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
@@ -106,8 +101,8 @@ __global__ __launch_bounds__(NT) void pool_bwd_kernel(const unsigned short* __re
             float f[4][8];
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                unpack8<DT>(*(const uint4*)(a + ((n * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + 8 * c8), f[k]);
-            unpack8<0>(*(const uint4*)(gp + ((n * Ho + yo) * Wo + xo) * C + 8 * c8), g);
+                gvf_unpack8<DT>(*(const uint4*)(a + ((n * H + 2 * yo + (k >> 1)) * W + 2 * xo + (k & 1)) * C + 8 * c8), f[k]);
+            gvf_unpack8<0>(*(const uint4*)(gp + ((n * Ho + yo) * Wo + xo) * C + 8 * c8), g);
             const int me = ((y & 1) << 1) | (x & 1);
 #pragma unroll
             for (int e = 0; e < 8; ++e) mine[e] = argmax4(f, e) == me;

@@ -9,6 +9,7 @@
 // float4 is used for loads and stores only; the arithmetic is per component (no packed fp32: _build.py).  Built with -ffp-contract=off:
 // every operation below rounds once, which is what the conformance bars of tests/test_optim_gpu.py count.
 #include "gvf_common.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_optim.h"
 
@@ -22,20 +23,6 @@ constexpr int CHUNK = 8192;        // elements per chunk
 constexpr int MAX_GRID = 1 << 20;  // workgroups per launch (grid-stride beyond)
 static_assert(CHUNK % 4 == 0 && CHUNK % (4 * NT) == 0, "chunk length");
 static_assert(sizeof(gvf_optim_tensor) == 72 && sizeof(gvf_optim_chunk) == 16 && sizeof(gvf_optim_record) == 128, "table layout");
-
-template <int THREADS>
-__device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = GVF_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, GVF_WAVE);
-    const int wave = threadIdx.x / GVF_WAVE;
-    if ((threadIdx.x & (GVF_WAVE - 1)) == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < THREADS / GVF_WAVE; ++w) s += red[w];
-    __syncthreads();
-    return s;   // valid in thread 0
-}
 
 // The data pointers come out of a table in memory, so the compiler cannot see that they are global: without the address-space casts
 // below every access would be a flat_ instruction (both counters, the aperture check) instead of a global_ one.
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(NT) void optim_norm_kernel(const gvf_optim_tensor* 
         const float* g = tensors[ck.tensor].g + ck.first;
         // the same elements per lane on either path: the partial does not depend on the alignment
         const double acc = aligned16(g) ? chunk_sumsq<true>(g, ck.count, inv) : chunk_sumsq<false>(g, ck.count, inv);
-        const double s = block_sum<NT>(acc, s_red);
+        const double s = gvf_block_sum_waves<NT>(acc, s_red);
         if (threadIdx.x == 0) part[c] = s;
     }
 }
@@ -125,7 +112,7 @@ __global__ __launch_bounds__(NT_FIN) void optim_finalize_kernel(const double* __
 #pragma unroll
         for (int u = 0; u < 4; ++u) s += x[u];      // index order within the lane
     }
-    s = block_sum<NT_FIN>(s, s_red);
+    s = gvf_block_sum_waves<NT_FIN>(s, s_red);
     if (threadIdx.x == 0) {
         const bool finite = isfinite(s);
         const float norm = (float)sqrt(s);

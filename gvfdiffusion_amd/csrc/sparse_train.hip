@@ -10,6 +10,7 @@
 #include <cmath>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_sparse_train.h"
@@ -20,18 +21,6 @@ constexpr int WG = 256;
 constexpr long long POST_PER_WG = 4096;           // elements of [T, L] per workgroup (posterior)
 constexpr long long REG_PER_WG = 1024;            // Gaussians per workgroup (regularisers: 4 per thread)
 constexpr int MAX_SCALARS = 2;
-
-template <int DT>
-__device__ __forceinline__ void unpack8(uint4 q, float (&f)[8]) {
-    f[0] = GvfLp<DT>::lo(q.x); f[1] = GvfLp<DT>::hi(q.x); f[2] = GvfLp<DT>::lo(q.y); f[3] = GvfLp<DT>::hi(q.y);
-    f[4] = GvfLp<DT>::lo(q.z); f[5] = GvfLp<DT>::hi(q.z); f[6] = GvfLp<DT>::lo(q.w); f[7] = GvfLp<DT>::hi(q.w);
-}
-template <int DT>
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    uint4 q;
-    q.x = GvfLp<DT>::pack(f[0], f[1]); q.y = GvfLp<DT>::pack(f[2], f[3]); q.z = GvfLp<DT>::pack(f[4], f[5]); q.w = GvfLp<DT>::pack(f[6], f[7]);
-    return q;
-}
 
 // ---- a. tanh-GELU -------------------------------------------------------------------------------------------------------------------------
 constexpr float GELU_K = 0.7978845608028654f, GELU_C = 0.044715f;
@@ -61,11 +50,11 @@ __global__ __launch_bounds__(WG) void gelu_kernel(const unsigned short* __restri
     const long long i = (long long)blockIdx.x * WG + threadIdx.x;
     if (i < nv) {
         float f[8], g[8], o[8];
-        unpack8<DT>(reinterpret_cast<const uint4*>(u)[i], f);
-        if (BWD) unpack8<DT>(reinterpret_cast<const uint4*>(da)[i], g);
+        gvf_unpack8<DT>(reinterpret_cast<const uint4*>(u)[i], f);
+        if (BWD) gvf_unpack8<DT>(reinterpret_cast<const uint4*>(da)[i], g);
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = BWD ? gelu_bwd(f[e], g[e]) : gelu_fwd(f[e]);
-        reinterpret_cast<uint4*>(out)[i] = pack8<DT>(o);
+        reinterpret_cast<uint4*>(out)[i] = gvf_pack8<DT>(o);
     }
     const long long t = nv * 8 + i;
     if (t < n) {
@@ -84,20 +73,7 @@ __global__ __launch_bounds__(WG) void gather_rows_kernel(const unsigned char* __
     out[t] = *reinterpret_cast<const uint4*>(src + index[i] * src_stride + c * 16);
 }
 
-// ---- sums: a workgroup's 256 double terms -> one slot; the slots -> the scalar ---------------------------------------------------------
-// a fixed tree over the threads, so a workgroup's partial does not depend on anything but its terms
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = WG / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
+// ---- sums: a workgroup's 256 double terms -> one slot (gvf_block_sum_tree); the slots -> the scalar ---------------------------------------
 // out[o] = factor[o] * (slots of scalar o in ascending order): thread k adds slots k, k + 256, ..., then the fixed tree.  blockIdx.x = o.
 struct SumJobs { float* out[MAX_SCALARS]; double factor[MAX_SCALARS]; };
 __global__ __launch_bounds__(WG) void sum_slots_kernel(const double* __restrict__ part, long long n_slots, SumJobs jobs) {
@@ -106,7 +82,7 @@ __global__ __launch_bounds__(WG) void sum_slots_kernel(const double* __restrict_
     if (jobs.out[o] == nullptr) return;
     double s = 0.0;
     for (long long w = threadIdx.x; w < n_slots; w += WG) s += part[(size_t)o * n_slots + w];
-    s = block_sum(s, red);
+    s = gvf_block_sum_tree<WG>(s, red);
     if (threadIdx.x == 0) *jobs.out[o] = (float)(s * jobs.factor[o]);
 }
 
@@ -145,7 +121,7 @@ __global__ __launch_bounds__(WG) void posterior_fwd_kernel(const float* __restri
             acc += (((double)(m * m) + (double)expf(lv)) - (double)lv) - 1.0;
         }
     }
-    acc = block_sum(acc, red);
+    acc = gvf_block_sum_tree<WG>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
@@ -238,8 +214,8 @@ __global__ __launch_bounds__(WG) void reg_fwd_kernel(const float* __restrict__ s
             reg_fwd_one(s, op[i], K, vol, opa);
         }
     }
-    vol = block_sum(vol, red);
-    opa = block_sum(opa, red);
+    vol = gvf_block_sum_tree<WG>(vol, red);
+    opa = gvf_block_sum_tree<WG>(opa, red);
     if (threadIdx.x == 0) { part[blockIdx.x] = vol; part[n_slots + blockIdx.x] = opa; }
 }
 
@@ -295,20 +271,17 @@ __global__ __launch_bounds__(WG) void colsum_final_kernel(const double* __restri
     out[c] = (float)s;
 }
 
-inline bool lp_ok(int dtype) { return dtype == GVF_DT_BF16 || dtype == GVF_DT_F16; }
-inline bool mis(const void* p, uintptr_t mask) { return (((uintptr_t)p) & mask) != 0; }
-inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 constexpr long long MAX_GRID = 0x7fffffffLL;
 
 template <bool BWD>
 int launch_gelu(int dtype, const void* u, const void* da, void* out, int64_t n, void* stream_) {
-    if (!lp_ok(dtype) || n < 0) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype) || n < 0) return GVF_EINVAL;
     if (n == 0) return GVF_OK;
     if (!u || !out || (BWD && !da)) return GVF_EINVAL;
-    if (mis(u, 1) || mis(out, 1) || mis(da, 1)) return GVF_EINVAL;
-    const bool vec = !mis(u, 15) && !mis(out, 15) && !mis(da, 15);
+    if (gvf_mis(u, 1) || gvf_mis(out, 1) || gvf_mis(da, 1)) return GVF_EINVAL;
+    const bool vec = !gvf_mis(u, 15) && !gvf_mis(out, 15) && !gvf_mis(da, 15);
     const long long nv = vec ? n / 8 : 0, tail = n - nv * 8;
-    const long long blocks = cdiv(nv > tail ? nv : tail, WG);
+    const long long blocks = gvf_cdiv(nv > tail ? nv : tail, WG);
     if (blocks > MAX_GRID) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
@@ -337,12 +310,12 @@ extern "C" int gvf_gather_rows(const void* src, int64_t src_stride_bytes, const 
     if (rows < 0 || width_bytes <= 0 || (width_bytes % 16) != 0) return GVF_EINVAL;
     if (src_stride_bytes < width_bytes || (src_stride_bytes % 16) != 0) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
-    if (!src || !index || !out || mis(src, 15) || mis(out, 15) || mis(index, 7)) return GVF_EINVAL;
+    if (!src || !index || !out || gvf_mis(src, 15) || gvf_mis(out, 15) || gvf_mis(index, 7)) return GVF_EINVAL;
     const long long cpr = width_bytes / 16;
     if (rows > (MAX_GRID * WG) / cpr) return GVF_EINVAL;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)cdiv(rows * cpr, WG)), dim3(WG), 0, stream, (const unsigned char*)src,
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)gvf_cdiv(rows * cpr, WG)), dim3(WG), 0, stream, (const unsigned char*)src,
                        (long long)src_stride_bytes, (const long long*)index, (uint4*)out, (long long)rows, cpr);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
@@ -353,7 +326,7 @@ static int posterior_dims_ok(int64_t T, int L) { return T >= 0 && L > 0 && T <= 
 
 extern "C" int gvf_posterior_workspace_bytes(int64_t T, int L, size_t* out) {
     if (!out || !posterior_dims_ok(T, L)) return GVF_EINVAL;
-    *out = (size_t)cdiv(T * (long long)L, POST_PER_WG) * sizeof(double);
+    *out = (size_t)gvf_cdiv(T * (long long)L, POST_PER_WG) * sizeof(double);
     return GVF_OK;
 }
 
@@ -361,11 +334,11 @@ extern "C" int gvf_posterior_fwd(const float* h, int64_t ldh, const float* eps, 
                                  size_t workspace_bytes, void* stream_) {
     if (!posterior_dims_ok(T, L) || T == 0) return GVF_EINVAL;
     if (!h || !eps || !z || !kl || !workspace) return GVF_EINVAL;
-    if (ldh < 2 * (int64_t)L || mis(h, 3) || mis(eps, 3) || mis(z, 3) || mis(kl, 3) || mis(workspace, 7)) return GVF_EINVAL;
+    if (ldh < 2 * (int64_t)L || gvf_mis(h, 3) || gvf_mis(eps, 3) || gvf_mis(z, 3) || gvf_mis(kl, 3) || gvf_mis(workspace, 7)) return GVF_EINVAL;
     size_t need = 0;
     if (gvf_posterior_workspace_bytes(T, L, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;
-    const long long total = T * (long long)L, slots = cdiv(total, POST_PER_WG);
-    const bool vec = (L % 4) == 0 && (ldh % 4) == 0 && !mis(h, 15) && !mis(eps, 15) && !mis(z, 15);
+    const long long total = T * (long long)L, slots = gvf_cdiv(total, POST_PER_WG);
+    const bool vec = (L % 4) == 0 && (ldh % 4) == 0 && !gvf_mis(h, 15) && !gvf_mis(eps, 15) && !gvf_mis(z, 15);
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     double* part = (double*)workspace;
@@ -383,14 +356,14 @@ extern "C" int gvf_posterior_bwd(const float* h, int64_t ldh, const float* eps, 
     if (!posterior_dims_ok(T, L)) return GVF_EINVAL;
     if (T == 0) return GVF_OK;
     if (!h || !dh || (dz != nullptr && !eps)) return GVF_EINVAL;
-    if (ldh < 2 * (int64_t)L || lddh < 2 * (int64_t)L || mis(h, 3) || mis(eps, 3) || mis(dz, 3) || mis(dkl, 3) || mis(dh, 3)) return GVF_EINVAL;
+    if (ldh < 2 * (int64_t)L || lddh < 2 * (int64_t)L || gvf_mis(h, 3) || gvf_mis(eps, 3) || gvf_mis(dz, 3) || gvf_mis(dkl, 3) || gvf_mis(dh, 3)) return GVF_EINVAL;
     const long long total = T * (long long)L;
-    const bool vec = (L % 4) == 0 && (ldh % 4) == 0 && (lddh % 4) == 0 && !mis(h, 15) && !mis(eps, 15) && !mis(dz, 15) && !mis(dh, 15);
+    const bool vec = (L % 4) == 0 && (ldh % 4) == 0 && (lddh % 4) == 0 && !gvf_mis(h, 15) && !gvf_mis(eps, 15) && !gvf_mis(dz, 15) && !gvf_mis(dh, 15);
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (vec) hipLaunchKernelGGL(posterior_bwd_kernel<true>, dim3((unsigned)cdiv(total / 4, WG)), dim3(WG), 0, stream, h, (long long)ldh, eps, dz, dkl, dh,
+    if (vec) hipLaunchKernelGGL(posterior_bwd_kernel<true>, dim3((unsigned)gvf_cdiv(total / 4, WG)), dim3(WG), 0, stream, h, (long long)ldh, eps, dz, dkl, dh,
                                 (long long)lddh, total, L);
-    else hipLaunchKernelGGL(posterior_bwd_kernel<false>, dim3((unsigned)cdiv(total, WG)), dim3(WG), 0, stream, h, (long long)ldh, eps, dz, dkl, dh,
+    else hipLaunchKernelGGL(posterior_bwd_kernel<false>, dim3((unsigned)gvf_cdiv(total, WG)), dim3(WG), 0, stream, h, (long long)ldh, eps, dz, dkl, dh,
                             (long long)lddh, total, L);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
@@ -402,7 +375,7 @@ static int reg_args_ok(int64_t N, float min_kernel_size, int activation) {
 
 extern "C" int gvf_gaussian_reg_workspace_bytes(int64_t N, size_t* out) {
     if (!out || N < 0 || N > MAX_GRID) return GVF_EINVAL;
-    *out = (size_t)MAX_SCALARS * (size_t)cdiv(N, REG_PER_WG) * sizeof(double);
+    *out = (size_t)MAX_SCALARS * (size_t)gvf_cdiv(N, REG_PER_WG) * sizeof(double);
     return GVF_OK;
 }
 
@@ -410,11 +383,11 @@ extern "C" int gvf_gaussian_reg_fwd(const float* scaling, const float* opacity, 
                                     int activation, float* vol, float* opa, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!reg_args_ok(N, min_kernel_size, activation) || N == 0) return GVF_EINVAL;
     if (!scaling || !opacity || !vol || !opa || !workspace) return GVF_EINVAL;
-    if (mis(scaling, 3) || mis(opacity, 3) || mis(vol, 3) || mis(opa, 3) || mis(workspace, 7)) return GVF_EINVAL;
+    if (gvf_mis(scaling, 3) || gvf_mis(opacity, 3) || gvf_mis(vol, 3) || gvf_mis(opa, 3) || gvf_mis(workspace, 7)) return GVF_EINVAL;
     size_t need = 0;
     if (gvf_gaussian_reg_workspace_bytes(N, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;
-    const long long slots = cdiv(N, REG_PER_WG);
-    const bool vec = !mis(scaling, 15) && !mis(opacity, 15);
+    const long long slots = gvf_cdiv(N, REG_PER_WG);
+    const bool vec = !gvf_mis(scaling, 15) && !gvf_mis(opacity, 15);
     const RegConst K = {scale_bias, opacity_bias, min_kernel_size * min_kernel_size, activation};
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
@@ -434,12 +407,12 @@ extern "C" int gvf_gaussian_reg_bwd(const float* scaling, const float* opacity, 
     if (N == 0) return GVF_OK;
     if (!scaling || !opacity) return GVF_EINVAL;
     if ((dvol != nullptr && !dscaling) || (dopa != nullptr && !dopacity) || (!dscaling && !dopacity)) return GVF_EINVAL;
-    if (mis(scaling, 3) || mis(opacity, 3) || mis(dvol, 3) || mis(dopa, 3) || mis(dscaling, 3) || mis(dopacity, 3)) return GVF_EINVAL;
-    const bool vec = !mis(scaling, 15) && !mis(opacity, 15) && !mis(dscaling, 15) && !mis(dopacity, 15);
+    if (gvf_mis(scaling, 3) || gvf_mis(opacity, 3) || gvf_mis(dvol, 3) || gvf_mis(dopa, 3) || gvf_mis(dscaling, 3) || gvf_mis(dopacity, 3)) return GVF_EINVAL;
+    const bool vec = !gvf_mis(scaling, 15) && !gvf_mis(opacity, 15) && !gvf_mis(dscaling, 15) && !gvf_mis(dopacity, 15);
     const RegConst K = {scale_bias, opacity_bias, min_kernel_size * min_kernel_size, activation};
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    const dim3 grid((unsigned)cdiv(N, REG_PER_WG));
+    const dim3 grid((unsigned)gvf_cdiv(N, REG_PER_WG));
     if (vec) hipLaunchKernelGGL(reg_bwd_kernel<true>, grid, dim3(WG), 0, stream, scaling, opacity, (long long)N, K, dvol, dopa, dscaling, dopacity);
     else hipLaunchKernelGGL(reg_bwd_kernel<false>, grid, dim3(WG), 0, stream, scaling, opacity, (long long)N, K, dvol, dopa, dscaling, dopacity);
     GVF_CHECK_LAUNCH();
@@ -448,18 +421,18 @@ extern "C" int gvf_gaussian_reg_bwd(const float* scaling, const float* opacity, 
 
 extern "C" int gvf_colsum_f32_workspace_bytes(int64_t rows, int C, size_t* out) {
     if (!out || rows < 0 || C <= 0 || rows > 65535 * COLSUM_ROWS) return GVF_EINVAL;
-    *out = (size_t)cdiv(rows, COLSUM_ROWS) * (size_t)C * sizeof(double);
+    *out = (size_t)gvf_cdiv(rows, COLSUM_ROWS) * (size_t)C * sizeof(double);
     return GVF_OK;
 }
 
 extern "C" int gvf_colsum_f32(const float* x, int64_t rows, int C, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
     size_t need = 0;
     if (gvf_colsum_f32_workspace_bytes(rows, C, &need) != GVF_OK || rows == 0) return GVF_EINVAL;
-    if (!x || !out || !workspace || workspace_bytes < need || mis(x, 3) || mis(out, 3) || mis(workspace, 7)) return GVF_EINVAL;
-    const long long chunks = cdiv(rows, COLSUM_ROWS);
+    if (!x || !out || !workspace || workspace_bytes < need || gvf_mis(x, 3) || gvf_mis(out, 3) || gvf_mis(workspace, 7)) return GVF_EINVAL;
+    const long long chunks = gvf_cdiv(rows, COLSUM_ROWS);
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    const unsigned gx = (unsigned)cdiv(C, WG);
+    const unsigned gx = (unsigned)gvf_cdiv(C, WG);
     hipLaunchKernelGGL(colsum_part_kernel, dim3(gx, (unsigned)chunks), dim3(WG), 0, stream, x, (long long)rows, C, (double*)workspace);
     GVF_CHECK_LAUNCH();
     hipLaunchKernelGGL(colsum_final_kernel, dim3(gx), dim3(WG), 0, stream, (const double*)workspace, chunks, C, out);

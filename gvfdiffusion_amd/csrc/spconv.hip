@@ -20,6 +20,7 @@
 // P ^ 1 (or the mirror image), whose positions P ^ {0, 1, 6, 7, 3, 2, 5, 4} are all different.
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_spconv.h"
@@ -235,24 +236,6 @@ __global__ __launch_bounds__(NT) void spconv3_kernel(const unsigned short* __res
 }
 
 // ---- LayerNorm + activation ----------------------------------------------------------------------------------------------------------------
-// Sum over the 64 lanes, every lane gets it (DPP / permlane data paths, as elem.hip)
-__device__ __forceinline__ float wave_sum(float v) {
-#define GVF_DPP(x_, ctrl_) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x_), ctrl_, 0xF, 0xF, false))
-    v += GVF_DPP(v, 0xB1);
-    v += GVF_DPP(v, 0x4E);
-    v += GVF_DPP(v, 0x141);
-    v += GVF_DPP(v, 0x140);
-#undef GVF_DPP
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    const auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    const unsigned a0 = r16[0], a1 = r16[1];
-    const float w = __uint_as_float(a0) + __uint_as_float(a1);
-    const unsigned uw = __builtin_bit_cast(unsigned, w);
-    const auto r32 = __builtin_amdgcn_permlane32_swap(uw, uw, false, false);
-    const unsigned b0 = r32[0], b1 = r32[1];
-    return __uint_as_float(b0) + __uint_as_float(b1);
-}
-
 // one wave per row; the row stays in registers: VPL float4 per lane, C <= 256 VPL.  The arithmetic is that of elem.hip's ln_mod_kernel
 // (the same rounding counts), with the activation on top.
 template <int VPL, int DT>
@@ -274,7 +257,7 @@ __global__ __launch_bounds__(NT) void ln_act_kernel(const float* __restrict__ x,
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
         }
     }
-    const float mean = wave_sum(s) / (float)C;
+    const float mean = gvf_wave_sum_dpp(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -283,7 +266,7 @@ __global__ __launch_bounds__(NT) void ln_act_kernel(const float* __restrict__ x,
             q += (a * a + b * b) + (c * c + d * d);
         }
     }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    const float rstd = rsqrtf(gvf_wave_sum_dpp(q) / (float)C + eps);
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
         if (lane + 64 * i >= nv) continue;

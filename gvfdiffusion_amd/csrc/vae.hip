@@ -8,19 +8,12 @@
 // of the to_q GEMM.  It depends on the static Gaussians only, so the host runs it once for all T frames.
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_vae.h"
 #include "../../include/gvf_dit.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 template <int DT>
 __global__ __launch_bounds__(256) void geglu_kernel(const unsigned short* __restrict__ in, int ld_in,
@@ -36,8 +29,8 @@ __global__ __launch_bounds__(256) void geglu_kernel(const unsigned short* __rest
         unsigned ow[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float lo = GvfLp<DT>::lo(aw[k]) * gelu_erf(GvfLp<DT>::lo(gw[k]));
-            const float hi = GvfLp<DT>::hi(aw[k]) * gelu_erf(GvfLp<DT>::hi(gw[k]));
+            const float lo = GvfLp<DT>::lo(aw[k]) * gvf_gelu_erf(GvfLp<DT>::lo(gw[k]));
+            const float hi = GvfLp<DT>::hi(aw[k]) * gvf_gelu_erf(GvfLp<DT>::hi(gw[k]));
             ow[k] = GvfLp<DT>::pack(lo, hi);
         }
         *reinterpret_cast<uint4*>(out + r * ld_out + c) = make_uint4(ow[0], ow[1], ow[2], ow[3]);
@@ -52,12 +45,12 @@ __device__ __forceinline__ void wave_layernorm(float (&v)[QE_MAXI], int ni, int 
 #pragma unroll
     for (int i = 0; i < QE_MAXI; ++i)
         if (i < ni && lane + 64 * i < C) s += v[i];
-    const float mean = wave_sum(s) / (float)C;
+    const float mean = gvf_wave_sum_xor(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < QE_MAXI; ++i)
         if (i < ni && lane + 64 * i < C) { const float d = v[i] - mean; q += d * d; }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    const float rstd = rsqrtf(gvf_wave_sum_xor(q) / (float)C + eps);
 #pragma unroll
     for (int i = 0; i < QE_MAXI; ++i) v[i] = (v[i] - mean) * rstd;
 }

@@ -11,6 +11,7 @@
 #include <cmath>
 #include "gvf_common.h"
 #include "gvf_lp.h"
+#include "gvf_rowops.h"
 #include "../../include/gvf_rast.h"
 #include "../../include/gvf_dit.h"
 #include "../../include/gvf_vae_train.h"
@@ -19,48 +20,14 @@ namespace {
 
 constexpr int WG = 256;
 
-template <int DT>
-__device__ __forceinline__ void unpack8(uint4 q, float (&f)[8]) {
-    f[0] = GvfLp<DT>::lo(q.x); f[1] = GvfLp<DT>::hi(q.x); f[2] = GvfLp<DT>::lo(q.y); f[3] = GvfLp<DT>::hi(q.y);
-    f[4] = GvfLp<DT>::lo(q.z); f[5] = GvfLp<DT>::hi(q.z); f[6] = GvfLp<DT>::lo(q.w); f[7] = GvfLp<DT>::hi(q.w);
-}
-template <int DT>
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-    uint4 q;
-    q.x = GvfLp<DT>::pack(f[0], f[1]); q.y = GvfLp<DT>::pack(f[2], f[3]); q.z = GvfLp<DT>::pack(f[4], f[5]); q.w = GvfLp<DT>::pack(f[6], f[7]);
-    return q;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// a fixed tree over the threads, so a workgroup's partial does not depend on anything but its terms
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = WG / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // ---- a. GEGLU -----------------------------------------------------------------------------------------------------------------------------
 constexpr float RSQRT2 = 0.70710678118654752440f, INV_SQRT_2PI = 0.39894228040143267794f, GEGLU_CUT = 14.0f;
-
-// the expression of csrc/vae.hip (the inference kernel): the training forward stores the same values
-__device__ __forceinline__ float gelu_erf(float g) { return 0.5f * g * (1.0f + erff(g * RSQRT2)); }
 
 __device__ __forceinline__ void geglu_bwd_one(float x, float g, float da, float& dx, float& dg) {
     const float cdf = 0.5f * (1.0f + erff(g * RSQRT2));
     // g phi(g): exp(-g^2 / 2) is 0 in fp32 long before g^2 overflows, and from |g| = 14 on the term (< 2e-42) is cut to an exact 0
     const float gp = fabsf(g) < GEGLU_CUT ? g * (INV_SQRT_2PI * __expf(-0.5f * (g * g))) : 0.0f;
-    dx = da * gelu_erf(g);
+    dx = da * gvf_gelu_erf(g);
     // x (Phi + g phi) can overflow for a bf16 x near the largest finite value; held at +-FLT_MAX so that a zero da gives 0 and not inf * 0
     const float p = fminf(fmaxf(x * (cdf + gp), -FLT_MAX), FLT_MAX);
     dg = da * p;
@@ -75,11 +42,11 @@ __global__ __launch_bounds__(WG) void geglu_fwd_kernel(const unsigned short* __r
     const long long r = i / f8;
     const int c = (int)(i - r * f8) << 3;
     float x[8], g[8], o[8];
-    unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + c), x);
-    unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + F + c), g);
+    gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + c), x);
+    gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + F + c), g);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = x[e] * gelu_erf(g[e]);
-    *reinterpret_cast<uint4*>(a + r * lda + c) = pack8<DT>(o);
+    for (int e = 0; e < 8; ++e) o[e] = x[e] * gvf_gelu_erf(g[e]);
+    *reinterpret_cast<uint4*>(a + r * lda + c) = gvf_pack8<DT>(o);
 }
 
 template <int DT>
@@ -90,13 +57,13 @@ __global__ __launch_bounds__(WG) void geglu_bwd_kernel(const unsigned short* __r
     const long long r = i / f8;
     const int c = (int)(i - r * f8) << 3;
     float x[8], g[8], d[8], dx[8], dg[8];
-    unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + c), x);
-    unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + F + c), g);
-    unpack8<DT>(*reinterpret_cast<const uint4*>(da + r * ldda + c), d);
+    gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + c), x);
+    gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(u + r * ldu + F + c), g);
+    gvf_unpack8<DT>(*reinterpret_cast<const uint4*>(da + r * ldda + c), d);
 #pragma unroll
     for (int e = 0; e < 8; ++e) geglu_bwd_one(x[e], g[e], d[e], dx[e], dg[e]);
-    *reinterpret_cast<uint4*>(du + r * lddu + c) = pack8<DT>(dx);
-    *reinterpret_cast<uint4*>(du + r * lddu + F + c) = pack8<DT>(dg);
+    *reinterpret_cast<uint4*>(du + r * lddu + c) = gvf_pack8<DT>(dx);
+    *reinterpret_cast<uint4*>(du + r * lddu + F + c) = gvf_pack8<DT>(dg);
 }
 
 // ---- b. embedding -------------------------------------------------------------------------------------------------------------------------
@@ -157,12 +124,12 @@ __device__ __forceinline__ float emb_layernorm(float (&t)[NI], int C, int lane, 
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < NI; ++i) sum += t[i];                          // channels >= C hold 0
-    const float mean = wave_sum(sum) / (float)C;
+    const float mean = gvf_wave_sum_xor(sum) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NI; ++i)
         if (lane + 64 * i < C) { const float d = t[i] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+    const float rstd = 1.0f / sqrtf(gvf_wave_sum_xor(q) / (float)C + eps);
 #pragma unroll
     for (int i = 0; i < NI; ++i) t[i] = lane + 64 * i < C ? (t[i] - mean) * rstd : 0.f;
     return rstd;
@@ -230,7 +197,7 @@ __global__ __launch_bounds__(WG) void embed_bwd_kernel(const float* __restrict__
             d[i] = c < C ? de[row * C + c] : 0.f;
             sd += d[i]; su += d[i] * u[i]; sv += d[i] * v[i];
         }
-        const float md = wave_sum(sd) * invC, au = wave_sum(su) * invC, av = wave_sum(sv) * invC;
+        const float md = gvf_wave_sum_xor(sd) * invC, au = gvf_wave_sum_xor(su) * invC, av = gvf_wave_sum_xor(sv) * invC;
         float t[EMB_MAXQ];
 #pragma unroll
         for (int k = 0; k < EMB_MAXQ; ++k) t[k] = 0.f;
@@ -349,7 +316,7 @@ __global__ __launch_bounds__(WG) void pg_fwd_kernel(const float* __restrict__ me
         }
         st<VW>(z + g * n + e, o);
     }
-    acc = block_sum(acc, red);
+    acc = gvf_block_sum_tree<WG>(acc, red);
     if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
@@ -401,9 +368,6 @@ __global__ __launch_bounds__(WG) void pg_bwd_kernel(const float* __restrict__ me
     st<VW>(dlogvar + gr * lddl + c, dl);
 }
 
-inline bool lp_ok(int dtype) { return dtype == GVF_DT_BF16 || dtype == GVF_DT_F16; }
-inline bool mis(const void* p, uintptr_t mask) { return (((uintptr_t)p) & mask) != 0; }
-inline long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
 constexpr long long MAX_GRID = 0x7fffffffLL;
 
 // rows * (F / 8) vectors, one thread each
@@ -415,7 +379,7 @@ inline bool embed_dims_ok(int64_t P, int qdim, int C) {
 // rows per workgroup: P / 512 rounded up to a multiple of the four waves, between 4 and EMB_MAX_ROWS -- a function of P alone, so the slots and
 // the order of every sum are the same run to run
 inline int emb_rows_per_wg(int64_t P) {
-    long long r = (cdiv(P, 512) + 3) / 4 * 4;
+    long long r = (gvf_cdiv(P, 512) + 3) / 4 * 4;
     return (int)(r < 4 ? 4 : (r > EMB_MAX_ROWS ? EMB_MAX_ROWS : r));
 }
 inline size_t embed_lds_bytes(int qdim, int C) { return ((size_t)C * (qdim | 1) + C + C / 6) * sizeof(float); }
@@ -428,14 +392,14 @@ inline bool pg_dims_ok(int64_t G, int64_t L, int Dl) {
 }  // namespace
 
 extern "C" int gvf_geglu_fwd(int dtype, const void* u, int64_t ldu, void* a, int64_t lda, int64_t rows, int F, void* stream_) {
-    if (!lp_ok(dtype) || !geglu_dims_ok(rows, F)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype) || !geglu_dims_ok(rows, F)) return GVF_EINVAL;
     if (ldu < 2 * (int64_t)F || lda < F || (ldu & 7) || (lda & 7)) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
-    if (!u || !a || mis(u, 15) || mis(a, 15)) return GVF_EINVAL;
+    if (!u || !a || gvf_mis(u, 15) || gvf_mis(a, 15)) return GVF_EINVAL;
     const int f8 = F >> 3;
     const long long total = rows * (long long)f8;
     (void)hipGetLastError();
-    GVF_LP_DISPATCH(dtype, hipLaunchKernelGGL(geglu_fwd_kernel<DT>, dim3((unsigned)cdiv(total, WG)), dim3(WG), 0, (hipStream_t)stream_,
+    GVF_LP_DISPATCH(dtype, hipLaunchKernelGGL(geglu_fwd_kernel<DT>, dim3((unsigned)gvf_cdiv(total, WG)), dim3(WG), 0, (hipStream_t)stream_,
                                               (const unsigned short*)u, (long long)ldu, (unsigned short*)a, (long long)lda, total, f8, F));
     GVF_CHECK_LAUNCH();
     return GVF_OK;
@@ -443,14 +407,14 @@ extern "C" int gvf_geglu_fwd(int dtype, const void* u, int64_t ldu, void* a, int
 
 extern "C" int gvf_geglu_bwd(int dtype, const void* u, int64_t ldu, const void* da, int64_t ldda, void* du, int64_t lddu, int64_t rows, int F,
                              void* stream_) {
-    if (!lp_ok(dtype) || !geglu_dims_ok(rows, F)) return GVF_EINVAL;
+    if (!gvf_lp_ok(dtype) || !geglu_dims_ok(rows, F)) return GVF_EINVAL;
     if (ldu < 2 * (int64_t)F || lddu < 2 * (int64_t)F || ldda < F || (ldu & 7) || (lddu & 7) || (ldda & 7)) return GVF_EINVAL;
     if (rows == 0) return GVF_OK;
-    if (!u || !da || !du || mis(u, 15) || mis(da, 15) || mis(du, 15)) return GVF_EINVAL;
+    if (!u || !da || !du || gvf_mis(u, 15) || gvf_mis(da, 15) || gvf_mis(du, 15)) return GVF_EINVAL;
     const int f8 = F >> 3;
     const long long total = rows * (long long)f8;
     (void)hipGetLastError();
-    GVF_LP_DISPATCH(dtype, hipLaunchKernelGGL(geglu_bwd_kernel<DT>, dim3((unsigned)cdiv(total, WG)), dim3(WG), 0, (hipStream_t)stream_,
+    GVF_LP_DISPATCH(dtype, hipLaunchKernelGGL(geglu_bwd_kernel<DT>, dim3((unsigned)gvf_cdiv(total, WG)), dim3(WG), 0, (hipStream_t)stream_,
                                               (const unsigned short*)u, (long long)ldu, (const unsigned short*)da, (long long)ldda,
                                               (unsigned short*)du, (long long)lddu, total, f8, F));
     GVF_CHECK_LAUNCH();
@@ -461,10 +425,10 @@ extern "C" int gvf_vae_embed_train_fwd(const float* r, int qdim, const float* W,
                                        float eps, void* stream_) {
     if (!embed_dims_ok(P, qdim, C) || !(eps >= 0.0f)) return GVF_EINVAL;
     if (P == 0) return GVF_OK;
-    if (!r || !W || !bias || !omega || !e || mis(r, 3) || mis(W, 3) || mis(bias, 3) || mis(omega, 3) || mis(e, 3)) return GVF_EINVAL;
+    if (!r || !W || !bias || !omega || !e || gvf_mis(r, 3) || gvf_mis(W, 3) || gvf_mis(bias, 3) || gvf_mis(omega, 3) || gvf_mis(e, 3)) return GVF_EINVAL;
     const size_t smem = embed_lds_bytes(qdim, C);
     const int rpw = emb_rows_per_wg(P);
-    const dim3 grid((unsigned)cdiv(P, rpw));
+    const dim3 grid((unsigned)gvf_cdiv(P, rpw));
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     if (C <= 192) hipLaunchKernelGGL(embed_fwd_kernel<3>, grid, dim3(WG), smem, stream, r, qdim, W, bias, omega, e, (long long)P, C, eps, rpw);
@@ -475,7 +439,7 @@ extern "C" int gvf_vae_embed_train_fwd(const float* r, int qdim, const float* W,
 
 extern "C" int gvf_vae_embed_bwd_workspace_bytes(int64_t P, int qdim, int C, size_t* out) {
     if (!out || !embed_dims_ok(P, qdim, C)) return GVF_EINVAL;
-    *out = (size_t)cdiv(P, emb_rows_per_wg(P)) * (size_t)(C * qdim + C) * sizeof(float);
+    *out = (size_t)gvf_cdiv(P, emb_rows_per_wg(P)) * (size_t)(C * qdim + C) * sizeof(float);
     return GVF_OK;
 }
 
@@ -484,27 +448,27 @@ extern "C" int gvf_vae_embed_bwd(const float* r, int qdim, const float* W, const
     if (!embed_dims_ok(P, qdim, C) || !(eps >= 0.0f)) return GVF_EINVAL;
     if (P == 0) return GVF_OK;
     if (!r || !W || !bias || !omega || !de || !dW || !db || !workspace) return GVF_EINVAL;
-    if (mis(r, 3) || mis(W, 3) || mis(bias, 3) || mis(omega, 3) || mis(de, 3) || mis(dW, 3) || mis(db, 3) || mis(dr, 3) || mis(workspace, 7))
+    if (gvf_mis(r, 3) || gvf_mis(W, 3) || gvf_mis(bias, 3) || gvf_mis(omega, 3) || gvf_mis(de, 3) || gvf_mis(dW, 3) || gvf_mis(db, 3) || gvf_mis(dr, 3) || gvf_mis(workspace, 7))
         return GVF_EINVAL;
     size_t need = 0;
     if (gvf_vae_embed_bwd_workspace_bytes(P, qdim, C, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;
     const size_t smem = embed_lds_bytes(qdim, C);
     const int rpw = emb_rows_per_wg(P);
-    const long long slots = cdiv(P, rpw);
+    const long long slots = gvf_cdiv(P, rpw);
     float* part = (float*)workspace;
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
     if (C <= 192) hipLaunchKernelGGL(embed_bwd_kernel<3>, dim3((unsigned)slots), dim3(WG), smem, stream, r, qdim, W, bias, omega, de, dr, part, (long long)P, C, eps, rpw);
     else hipLaunchKernelGGL(embed_bwd_kernel<12>, dim3((unsigned)slots), dim3(WG), smem, stream, r, qdim, W, bias, omega, de, dr, part, (long long)P, C, eps, rpw);
     GVF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(embed_final_kernel, dim3((unsigned)cdiv(C * qdim + C, WG)), dim3(WG), 0, stream, (const float*)part, slots, C * qdim, C, dW, db);
+    hipLaunchKernelGGL(embed_final_kernel, dim3((unsigned)gvf_cdiv(C * qdim + C, WG)), dim3(WG), 0, stream, (const float*)part, slots, C * qdim, C, dW, db);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
 }
 
 extern "C" int gvf_posterior_groups_workspace_bytes(int64_t G, int64_t L, int Dl, size_t* out) {
     if (!out || !pg_dims_ok(G, L, Dl)) return GVF_EINVAL;
-    *out = (size_t)G * (size_t)cdiv(L * (long long)Dl, PG_PER_WG) * sizeof(double);
+    *out = (size_t)G * (size_t)gvf_cdiv(L * (long long)Dl, PG_PER_WG) * sizeof(double);
     return GVF_OK;
 }
 
@@ -513,12 +477,12 @@ extern "C" int gvf_posterior_groups_fwd(const float* mean, int64_t ld_mean, cons
     if (!pg_dims_ok(G, L, Dl) || ld_mean < Dl || ld_logvar < Dl) return GVF_EINVAL;
     if (G == 0) return GVF_OK;
     if (!mean || !logvar || !eps || !z || !kl || !workspace) return GVF_EINVAL;
-    if (mis(mean, 3) || mis(logvar, 3) || mis(eps, 3) || mis(z, 3) || mis(kl, 3) || mis(workspace, 7)) return GVF_EINVAL;
+    if (gvf_mis(mean, 3) || gvf_mis(logvar, 3) || gvf_mis(eps, 3) || gvf_mis(z, 3) || gvf_mis(kl, 3) || gvf_mis(workspace, 7)) return GVF_EINVAL;
     size_t need = 0;
     if (gvf_posterior_groups_workspace_bytes(G, L, Dl, &need) != GVF_OK || workspace_bytes < need) return GVF_EINVAL;
-    const long long n = L * (long long)Dl, slots = cdiv(n, PG_PER_WG);
+    const long long n = L * (long long)Dl, slots = gvf_cdiv(n, PG_PER_WG);
     if (G * slots > MAX_GRID) return GVF_EINVAL;
-    const bool vec = (Dl % 4) == 0 && (ld_mean % 4) == 0 && (ld_logvar % 4) == 0 && !mis(mean, 15) && !mis(logvar, 15) && !mis(eps, 15) && !mis(z, 15);
+    const bool vec = (Dl % 4) == 0 && (ld_mean % 4) == 0 && (ld_logvar % 4) == 0 && !gvf_mis(mean, 15) && !gvf_mis(logvar, 15) && !gvf_mis(eps, 15) && !gvf_mis(z, 15);
     hipStream_t stream = (hipStream_t)stream_;
     double* part = (double*)workspace;
     (void)hipGetLastError();
@@ -527,7 +491,7 @@ extern "C" int gvf_posterior_groups_fwd(const float* mean, int64_t ld_mean, cons
     else hipLaunchKernelGGL(pg_fwd_kernel<1>, dim3((unsigned)(G * slots)), dim3(WG), 0, stream, mean, (long long)ld_mean, logvar, (long long)ld_logvar, eps, z,
                             n, (long long)L, Dl, slots, part);
     GVF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pg_final_kernel, dim3((unsigned)cdiv(G, WG)), dim3(WG), 0, stream, (const double*)part, slots, (long long)G, 0.5 / (double)n, kl);
+    hipLaunchKernelGGL(pg_final_kernel, dim3((unsigned)gvf_cdiv(G, WG)), dim3(WG), 0, stream, (const double*)part, slots, (long long)G, 0.5 / (double)n, kl);
     GVF_CHECK_LAUNCH();
     return GVF_OK;
 }
@@ -538,15 +502,15 @@ extern "C" int gvf_posterior_groups_bwd(const float* mean, int64_t ld_mean, cons
     if (!pg_dims_ok(G, L, Dl) || ld_mean < Dl || ld_logvar < Dl || ld_dmean < Dl || ld_dlogvar < Dl) return GVF_EINVAL;
     if (G == 0) return GVF_OK;
     if (!mean || !logvar || !dmean || !dlogvar || (dz != nullptr && !eps)) return GVF_EINVAL;
-    if (mis(mean, 3) || mis(logvar, 3) || mis(eps, 3) || mis(dz, 3) || mis(dkl, 3) || mis(dmean, 3) || mis(dlogvar, 3)) return GVF_EINVAL;
+    if (gvf_mis(mean, 3) || gvf_mis(logvar, 3) || gvf_mis(eps, 3) || gvf_mis(dz, 3) || gvf_mis(dkl, 3) || gvf_mis(dmean, 3) || gvf_mis(dlogvar, 3)) return GVF_EINVAL;
     const long long n = L * (long long)Dl, total = G * n;
-    const bool vec = (Dl % 4) == 0 && (ld_mean % 4) == 0 && (ld_logvar % 4) == 0 && (ld_dmean % 4) == 0 && (ld_dlogvar % 4) == 0 && !mis(mean, 15) &&
-                     !mis(logvar, 15) && !mis(eps, 15) && !mis(dz, 15) && !mis(dmean, 15) && !mis(dlogvar, 15);
+    const bool vec = (Dl % 4) == 0 && (ld_mean % 4) == 0 && (ld_logvar % 4) == 0 && (ld_dmean % 4) == 0 && (ld_dlogvar % 4) == 0 && !gvf_mis(mean, 15) &&
+                     !gvf_mis(logvar, 15) && !gvf_mis(eps, 15) && !gvf_mis(dz, 15) && !gvf_mis(dmean, 15) && !gvf_mis(dlogvar, 15);
     hipStream_t stream = (hipStream_t)stream_;
     (void)hipGetLastError();
-    if (vec) hipLaunchKernelGGL(pg_bwd_kernel<4>, dim3((unsigned)cdiv(total / 4, WG)), dim3(WG), 0, stream, mean, (long long)ld_mean, logvar,
+    if (vec) hipLaunchKernelGGL(pg_bwd_kernel<4>, dim3((unsigned)gvf_cdiv(total / 4, WG)), dim3(WG), 0, stream, mean, (long long)ld_mean, logvar,
                                 (long long)ld_logvar, eps, dz, dkl, dmean, (long long)ld_dmean, dlogvar, (long long)ld_dlogvar, total, n, (long long)L, Dl);
-    else hipLaunchKernelGGL(pg_bwd_kernel<1>, dim3((unsigned)cdiv(total, WG)), dim3(WG), 0, stream, mean, (long long)ld_mean, logvar, (long long)ld_logvar,
+    else hipLaunchKernelGGL(pg_bwd_kernel<1>, dim3((unsigned)gvf_cdiv(total, WG)), dim3(WG), 0, stream, mean, (long long)ld_mean, logvar, (long long)ld_logvar,
                             eps, dz, dkl, dmean, (long long)ld_dmean, dlogvar, (long long)ld_dlogvar, total, n, (long long)L, Dl);
     GVF_CHECK_LAUNCH();
     return GVF_OK;

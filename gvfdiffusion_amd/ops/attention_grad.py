@@ -10,7 +10,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from . import dit_ops
+from . import _util, dit_ops
 
 _vp, _i, _i64, _sz, _f, _ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_longlong
 
@@ -39,9 +39,7 @@ def _layout(t):
 
 
 def workspace_bytes(N: int, Lq: int, Lk: int, H: int, C: int) -> int:
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().gvf_attn_bwd_workspace_bytes(N, 1, Lq, Lk, H, C, ctypes.byref(nb)), "gvf_attn_bwd_workspace_bytes")
-    return int(nb.value)
+    return _util.workspace_bytes("gvf_attn_bwd_workspace_bytes", N, 1, Lq, Lk, H, C)
 
 
 def attention_backward(q, k, v, out, dout, scale: float):
@@ -55,7 +53,7 @@ def attention_backward(q, k, v, out, dout, scale: float):
     if N == 0 or Lq == 0 or Lk == 0 or H == 0:          # nothing attends to anything: zero gradients, no launch
         return dq.zero_(), dk.zero_(), dv.zero_()
     q, k, v, out, dout = (_layout(t) for t in (q, k, v, out, dout))
-    ws = torch.empty(workspace_bytes(N, Lq, Lk, H, C), dtype=torch.uint8, device=q.device)
+    ws = _util.scratch("gvf_attn_bwd_workspace_bytes", q.device, N, 1, Lq, Lk, H, C)
     _lib.check(_lib.lib().gvf_attn_bwd(dt, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(dq), _lib.ptr(dk),
                                        _lib.ptr(dv), N, 1, Lq, Lk, H, C, _s4(q), _s4(k), _s4(v), _s4(out), _s4(dout), _s4(dq), _s4(dk), _s4(dv),
                                        float(scale), _lib.ptr(ws), ws.numel(), _lib.current_stream(q.device)), "gvf_attn_bwd")
@@ -132,10 +130,7 @@ def _check_cu(cu_q, cu_k):
 
 
 def varlen_workspace_bytes(n_seqs: int, total_q: int, total_k: int, max_Lq: int, max_Lk: int, H: int, C: int) -> int:
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().gvf_attn_varlen_bwd_workspace_bytes(n_seqs, total_q, total_k, max_Lq, max_Lk, H, C, ctypes.byref(nb)),
-               "gvf_attn_varlen_bwd_workspace_bytes")
-    return int(nb.value)
+    return _util.workspace_bytes("gvf_attn_varlen_bwd_workspace_bytes", n_seqs, total_q, total_k, max_Lq, max_Lk, H, C)
 
 
 def attention_varlen_backward(q, k, v, out, dout, cu_q, cu_k, max_Lq: int, max_Lk: int, scale: float, workspace=None, grads=None):
@@ -163,7 +158,7 @@ def attention_varlen_backward(q, k, v, out, dout, cu_q, cu_k, max_Lq: int, max_L
     q, k, v, out, dout = (_layout3(t) for t in (q, k, v, out, dout))
     n_seqs = cu_q.numel() - 1
     if workspace is None:
-        workspace = torch.empty(varlen_workspace_bytes(n_seqs, Tq, Tk, int(max_Lq), int(max_Lk), H, C), dtype=torch.uint8, device=q.device)
+        workspace = _util.scratch("gvf_attn_varlen_bwd_workspace_bytes", q.device, n_seqs, Tq, Tk, int(max_Lq), int(max_Lk), H, C)
     _lib.check(_lib.lib().gvf_attn_varlen_bwd(dt, _lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(out), _lib.ptr(dout), _lib.ptr(dq), _lib.ptr(dk),
                                               _lib.ptr(dv), n_seqs, _lib.ptr(cu_q), _lib.ptr(cu_k), Tq, Tk, int(max_Lq), int(max_Lk), H, C,
                                               _s43(q), _s43(k), _s43(v), _s43(out), _s43(dout), _s43(dq), _s43(dk), _s43(dv), float(scale),

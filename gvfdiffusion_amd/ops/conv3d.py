@@ -12,6 +12,8 @@ import ctypes
 import torch
 
 from .. import _lib
+from . import _util
+from ._util import stream as _stream
 from .dit_ops import dt_code
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
@@ -28,14 +30,8 @@ _lib.register({
 })
 
 
-def _stream(t):
-    return _lib.current_stream(t.device)
-
-
 def packed_bytes(cout: int, cin: int) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_conv3d3_packed_bytes(int(cout), int(cin), ctypes.byref(nb)), "gvf_conv3d3_packed_bytes")
-    return nb.value
+    return _util.workspace_bytes("gvf_conv3d3_packed_bytes", int(cout), int(cin))
 
 
 def pack_weight(w: torch.Tensor, dtype) -> torch.Tensor:
@@ -89,9 +85,7 @@ def conv3(x: torch.Tensor, grid, wimg: torch.Tensor, cin: int, cout: int, bias=N
 
 
 def occupancy_workspace_bytes(cells: int) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_occupancy_workspace_bytes(int(cells), ctypes.byref(nb)), "gvf_occupancy_workspace_bytes")
-    return nb.value
+    return _util.workspace_bytes("gvf_occupancy_workspace_bytes", int(cells))
 
 
 def occupancy_coords(logits: torch.Tensor, grid) -> torch.Tensor:
@@ -102,7 +96,7 @@ def occupancy_coords(logits: torch.Tensor, grid) -> torch.Tensor:
     cells = B * X * Y * Z
     if logits.dtype != torch.float32 or logits.numel() != cells or not logits.is_contiguous():
         raise ValueError(f"conv3d: occupancy takes {cells} contiguous fp32 logits for the grid {(B, X, Y, Z)}, got {logits.dtype} {tuple(logits.shape)}")
-    ws = torch.empty(occupancy_workspace_bytes(cells), dtype=torch.uint8, device=logits.device)
+    ws = _util.scratch("gvf_occupancy_workspace_bytes", logits.device, cells)
     coords = torch.empty((cells, 4), dtype=torch.int32, device=logits.device)
     count = torch.empty(1, dtype=torch.int32, device=logits.device)
     _lib.check(_lib.lib().gvf_occupancy_coords(_lib.ptr(logits), B, X, Y, Z, _lib.ptr(coords), cells, _lib.ptr(count), _lib.ptr(ws), ws.numel(),

@@ -8,6 +8,7 @@ import os
 import torch
 
 from .. import _lib
+from ._util import ptr as _p, stream as _stream
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
@@ -107,14 +108,6 @@ _PAIRS = {
 }
 _lib.register({new: (_i, [_i] + args) for (new, _old), args in _PAIRS.items()})
 _lib.register({old: (_i, args) for (_new, old), args in _PAIRS.items()})
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream(t):
-    return _lib.current_stream(t.device)
 
 
 def pad64(k: int) -> int:

@@ -13,9 +13,9 @@ import torch
 
 from .. import _lib
 from . import dit_ops
+from ._util import psz as _psz, ptr as _p, scratch as _scratch
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
-_psz = ctypes.POINTER(_sz)
 
 _lib.register({
     "gvf_ln_mod_bwd_workspace_bytes": (_i, [_i, _i, _i, _psz]),
@@ -27,14 +27,6 @@ _lib.register({
     "gvf_rmsnorm_heads_bwd_workspace_bytes": (_i, [_i, _i, _i, _psz]),
     "gvf_rmsnorm_heads_bwd": (_i, [_i, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _vp, _sz, _vp]),
 })
-
-_p = _lib.ptr
-
-
-def _workspace(fn_name, dev, *dims):
-    nb = _sz(0)
-    _lib.check(getattr(_lib.lib(), fn_name)(*dims, ctypes.byref(nb)), fn_name)
-    return torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
 
 
 def _table_view(t, name, G, C):
@@ -90,7 +82,7 @@ class _LayerNormModulateFn(torch.autograd.Function):
         dw = torch.zeros(C, dtype=torch.float32, device=dev) if ln_w is not None else None
         db = torch.zeros(C, dtype=torch.float32, device=dev) if ln_w is not None else None
         if rows > 0:
-            ws = _workspace("gvf_ln_mod_bwd_workspace_bytes", dev, rows, C, ctx.rpg if scale is not None else 0)
+            ws = _scratch("gvf_ln_mod_bwd_workspace_bytes", dev, rows, C, ctx.rpg if scale is not None else 0)
             _lib.check(_lib.lib().gvf_ln_mod_bwd(dit_ops.dt_code(dy2.dtype), _p(x2), _p(dy2), _p(dres), _p(dx), rows, C, float(ctx.eps), _p(ln_w), _p(ln_b),
                                                  _p(scale), ctx.mod_ld, ctx.rpg, _p(dshift), _p(dscale), _p(dw), _p(db), _p(ws), ws.numel(),
                                                  _lib.current_stream(dev)), "gvf_ln_mod_bwd")
@@ -161,7 +153,7 @@ class _GateResidualFn(torch.autograd.Function):
             G = max(1, (rows + ctx.rpg - 1) // ctx.rpg) if gate is not None else 0
             dgate = torch.zeros((G, C), dtype=torch.float32, device=dev) if gate is not None else None
             if rows > 0:
-                ws = _workspace("gvf_gate_residual_bwd_workspace_bytes", dev, rows, C, ctx.rpg if gate is not None else 0)
+                ws = _scratch("gvf_gate_residual_bwd_workspace_bytes", dev, rows, C, ctx.rpg if gate is not None else 0)
                 _lib.check(_lib.lib().gvf_gate_residual_bwd(dit_ops.dt_code(ctx.h_dtype), _p(dout), _p(h), _p(gate), ctx.gate_ld, ctx.rpg, _p(dh), _p(dgate),
                                                             rows, C, _p(ws), ws.numel(), _lib.current_stream(dev)), "gvf_gate_residual_bwd")
         # the gradient of x is dout itself: the same tensor, no copy
@@ -224,7 +216,7 @@ class _RmsNormHeadsFn(torch.autograd.Function):
         dx = torch.empty(xv.shape, dtype=xv.dtype, device=dev)
         dgamma = torch.zeros((H, d), dtype=torch.float32, device=dev)
         if rows > 0:
-            ws = _workspace("gvf_rmsnorm_heads_bwd_workspace_bytes", dev, rows, H, d)
+            ws = _scratch("gvf_rmsnorm_heads_bwd_workspace_bytes", dev, rows, H, d)
             _lib.check(_lib.lib().gvf_rmsnorm_heads_bwd(dit_ops.dt_code(xv.dtype), _p(xv), ctx.ldx, _p(dyv), lddy, _p(gamma), _p(dx), H * d, _p(dgamma),
                                                         rows, H, d, _p(ws), ws.numel(), _lib.current_stream(dev)), "gvf_rmsnorm_heads_bwd")
         need = ctx.needs_input_grad

@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from ._util import f32c as _f32c, scratch as _scratch
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
@@ -27,12 +28,6 @@ def window_taps() -> torch.Tensor:
     return torch.tensor(list(buf), dtype=torch.float32)
 
 
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
-
-
 def _planes(pred: torch.Tensor, target: torch.Tensor):
     if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
         raise TypeError("image_loss: pred and target must be tensors")
@@ -50,12 +45,6 @@ def _planes(pred: torch.Tensor, target: torch.Tensor):
     return planes, H, W
 
 
-def _scratch(planes, H, W, flags, device):
-    nb = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().gvf_image_loss_scratch_bytes(planes, H, W, flags, ctypes.byref(nb)), "gvf_image_loss_scratch_bytes")
-    return torch.empty(nb.value, dtype=torch.uint8, device=device)
-
-
 class _ImageLossFn(torch.autograd.Function):
     """(pred, target) -> (loss, mean L1, mean SSIM); the gradient flows to pred only.  keep_ssim: the forward keeps the SSIM
     partial maps for the backward (needed whenever the SSIM term can reach the gradient)."""
@@ -64,7 +53,7 @@ class _ImageLossFn(torch.autograd.Function):
     def forward(ctx, pred, target, w_l1: float, w_ssim: float, keep_ssim: bool):
         planes, H, W = _planes(pred, target)
         flags = SSIM_GRAD if (keep_ssim and ctx.needs_input_grad[0]) else 0
-        scratch = _scratch(planes, H, W, flags, pred.device)
+        scratch = _scratch("gvf_image_loss_scratch_bytes", pred.device, planes, H, W, flags)
         terms = torch.empty(3, dtype=torch.float32, device=pred.device)
         l = _lib.lib()
         _lib.check(l.gvf_image_loss_forward(_lib.ptr(pred), _lib.ptr(target), planes, H, W, float(w_l1), float(w_ssim), _lib.ptr(terms),

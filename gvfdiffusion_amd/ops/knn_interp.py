@@ -7,6 +7,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from ._util import f32c as _f32c, scratch as _scratch
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
@@ -19,12 +20,6 @@ _lib.register({
     "gvf_interp_loss_forward": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gvf_interp_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i64, _i, _vp]),
 })
-
-
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t.contiguous()
 
 
 def _check(name, q, a, m, lengths, k, pred=None):
@@ -142,9 +137,7 @@ class _InterpL1Fn(torch.autograd.Function):
             stride = 3
         dev = pred.device
         l = _lib.lib()
-        nb = ctypes.c_size_t(0)
-        _lib.check(l.gvf_interp_loss_scratch_bytes(B, T, P, ctypes.byref(nb)), "gvf_interp_loss_scratch_bytes")
-        scratch = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+        scratch = _scratch("gvf_interp_loss_scratch_bytes", dev, B, T, P)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         est = torch.empty((B, T, P, 3), dtype=torch.float32, device=dev) if want_est else None
         need_grad = ctx.needs_input_grad[0]

@@ -13,7 +13,8 @@ import ctypes
 import torch
 
 from .. import _lib
-from . import dit_ops
+from . import _util, dit_ops
+from ._util import ptr as _p
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
@@ -23,8 +24,6 @@ _lib.register({
     "gvf_gemm_wgrad_workspace_bytes": (_i, [_i, _i, _i, _i, ctypes.POINTER(_sz)]),
     "gvf_gemm_wgrad": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _i, _vp]),
 })
-
-_p = _lib.ptr
 
 
 def _pad8(n: int) -> int:
@@ -67,16 +66,13 @@ def wgrad_splits(M: int, N: int, K: int) -> int:
 
 
 def wgrad_workspace_bytes(M: int, N: int, K: int, splits: int = 0) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_gemm_wgrad_workspace_bytes(M, N, K, splits, ctypes.byref(nb)), "gvf_gemm_wgrad_workspace_bytes")
-    return int(nb.value)
+    return _util.workspace_bytes("gvf_gemm_wgrad_workspace_bytes", M, N, K, splits)
 
 
 def _rows2d(t, name):
     if t.dim() != 2:
         raise ValueError(f"wgrad: {name} must be a 2-D tensor, got {tuple(t.shape)}")
-    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % 8 != 0)) or t.data_ptr() % 16 != 0:
-        t = t.contiguous()
+    t = _util.rows16(t)
     return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
 
 
@@ -107,7 +103,7 @@ def wgrad(dy, x, bias=True, splits=0, out=None, out_bias=None, workspace=None):
             db.zero_()
         return dw, db
     if workspace is None:
-        workspace = torch.empty(wgrad_workspace_bytes(M, N, K, splits), dtype=torch.uint8, device=dev)
+        workspace = _util.scratch("gvf_gemm_wgrad_workspace_bytes", dev, M, N, K, splits)
     _lib.check(_lib.lib().gvf_gemm_wgrad(dt, _p(dy), ldy, _p(x), ldx, M, N, K, _p(dw), dw.stride(0) if N > 1 else K, _p(db), _p(workspace),
                                          workspace.numel() * workspace.element_size(), int(splits), _lib.current_stream(dev)), "gvf_gemm_wgrad")
     return dw, db

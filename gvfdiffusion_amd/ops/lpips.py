@@ -13,7 +13,8 @@ import torch
 from torch import nn
 
 from .. import _lib
-from . import precision
+from . import _util, precision
+from ._util import stream as _stream
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
@@ -52,10 +53,6 @@ def _dt(dtype) -> int:
     raise ValueError(f"lpips: the operand type must be torch.float16 or torch.bfloat16, got {dtype}")
 
 
-def _stream(t):
-    return _lib.current_stream(t.device)
-
-
 def _nhwc(t, what, C=None):
     _lib.require_cuda(t)
     if t.dim() != 4 or not t.is_contiguous() or (C is not None and t.shape[3] != C):
@@ -66,9 +63,7 @@ def _nhwc(t, what, C=None):
 # ---- per-layer wrappers ---------------------------------------------------------------------------------------------------------------
 
 def packed_bytes(cout: int, cin: int, mode: int = PACK_FWD) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_conv3x3_packed_bytes(cout, cin, mode, ctypes.byref(nb)), "gvf_conv3x3_packed_bytes")
-    return nb.value
+    return _util.workspace_bytes("gvf_conv3x3_packed_bytes", cout, cin, mode)
 
 
 def pack_conv(weight: torch.Tensor, mode: int, dtype) -> torch.Tensor:
@@ -157,9 +152,7 @@ def _tap_args(ax, ay, lin):
 def tap_forward(ax: torch.Tensor, ay: torch.Tensor, lin: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """The N per-image terms of one tap (fp32)."""
     N, H, W, C = _tap_args(ax, ay, lin)
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_lpips_tap_scratch_bytes(N, H, W, ctypes.byref(nb)), "gvf_lpips_tap_scratch_bytes")
-    scratch = torch.empty(nb.value, dtype=torch.uint8, device=ax.device)
+    scratch = _util.scratch("gvf_lpips_tap_scratch_bytes", ax.device, N, H, W)
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=ax.device)
     _lib.check(_lib.lib().gvf_lpips_tap_forward(_lib.ptr(ax), _lib.ptr(ay), _lib.ptr(lin), N, H, W, C, _dt(ax.dtype), _lib.ptr(out),

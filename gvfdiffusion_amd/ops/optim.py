@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import _util
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
 
@@ -201,9 +202,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.n_chunks == 0:
             raise ValueError("FusedAdamW: every parameter is empty")
         self._chunks = torch.from_numpy(chunks.view(np.uint8).copy()).to(self.device)
-        nb = ctypes.c_size_t(0)
-        _lib.check(_lib.lib().gvf_optim_scratch_bytes(self.n_chunks, ctypes.byref(nb)), "gvf_optim_scratch_bytes")
-        self._scratch = torch.zeros(nb.value, dtype=torch.uint8, device=self.device)
+        # not _util.scratch: kept for the optimizer's lifetime and zero-filled, at the exact size
+        self._scratch = torch.zeros(_util.workspace_bytes("gvf_optim_scratch_bytes", self.n_chunks), dtype=torch.uint8, device=self.device)
         self._record = torch.zeros(RECORD_BYTES, dtype=torch.uint8, device=self.device)
         self._table = torch.zeros(len(self._params) * TENSOR_DTYPE.itemsize, dtype=torch.uint8, device=self.device)
         self._table_ptrs = None

@@ -15,9 +15,9 @@ import torch
 
 from .. import _lib
 from . import dit_ops
+from ._util import psz as _psz, ptr as _p, rows16 as _rows16, scratch as _scratch
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
-_psz = ctypes.POINTER(_sz)
 
 _lib.register({
     "gvf_gelu_tanh_fwd": (_i, [_i, _vp, _vp, _i64, _vp]),
@@ -33,14 +33,7 @@ _lib.register({
     "gvf_colsum_f32": (_i, [_vp, _i64, _i, _vp, _vp, _sz, _vp]),
 })
 
-_p = _lib.ptr
 ACTIVATIONS = {"exp": 0, "softplus": 1}
-
-
-def _workspace(fn_name, dev, *dims):
-    nb = _sz(0)
-    _lib.check(getattr(_lib.lib(), fn_name)(*dims, ctypes.byref(nb)), fn_name)
-    return torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
 
 
 # ---- tanh-GELU ----------------------------------------------------------------------------------------------------------------------------
@@ -83,7 +76,7 @@ def colsum(x):
         raise ValueError(f"colsum: x must be a non-empty fp32 [rows, C] tensor, got {x.dtype} {tuple(x.shape)}")
     x = x.contiguous()
     out = torch.empty(x.shape[1], dtype=torch.float32, device=x.device)
-    ws = _workspace("gvf_colsum_f32_workspace_bytes", x.device, x.shape[0], x.shape[1])
+    ws = _scratch("gvf_colsum_f32_workspace_bytes", x.device, x.shape[0], x.shape[1])
     _lib.check(_lib.lib().gvf_colsum_f32(_p(x), x.shape[0], x.shape[1], _p(out), _p(ws), ws.numel(), _lib.current_stream(x.device)), "gvf_colsum_f32")
     return out
 
@@ -117,14 +110,6 @@ def _gather_launch(x, index, out):
         _lib.check(_lib.lib().gvf_gather_rows(_p(x), (x.stride(0) if x.shape[0] > 1 else x.shape[1]) * es, _p(index), _p(out), rows, x.shape[1] * es,
                                               _lib.current_stream(x.device)), "gvf_gather_rows")
     return out
-
-
-def _rows16(x):
-    """a 2-D tensor as the kernel addresses it: unit column stride, row stride and base multiples of 16 bytes; else a copy"""
-    es = x.element_size()
-    if x.stride(1) != 1 or (x.shape[0] > 1 and (x.stride(0) < x.shape[1] or (x.stride(0) * es) % 16 != 0)) or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
-    return x
 
 
 class _GatherRowsFn(torch.autograd.Function):
@@ -182,7 +167,7 @@ class _PosteriorFn(torch.autograd.Function):
         dev = h.device
         z = torch.empty((T, L), dtype=torch.float32, device=dev)
         kl = torch.empty((), dtype=torch.float32, device=dev)
-        ws = _workspace("gvf_posterior_workspace_bytes", dev, T, L)
+        ws = _scratch("gvf_posterior_workspace_bytes", dev, T, L)
         _lib.check(_lib.lib().gvf_posterior_fwd(_p(hv), ldh, _p(eps), _p(z), _p(kl), T, L, _p(ws), ws.numel(), _lib.current_stream(dev)), "gvf_posterior_fwd")
         ctx.save_for_backward(hv, eps)
         ctx.ldh = ldh
@@ -224,7 +209,7 @@ class _GaussianRegFn(torch.autograd.Function):
     def forward(ctx, scaling, opacity, bs, bo, kappa, act):
         N, dev = scaling.shape[0], scaling.device
         out = torch.empty(2, dtype=torch.float32, device=dev)
-        ws = _workspace("gvf_gaussian_reg_workspace_bytes", dev, N)
+        ws = _scratch("gvf_gaussian_reg_workspace_bytes", dev, N)
         _lib.check(_lib.lib().gvf_gaussian_reg_fwd(_p(scaling), _p(opacity), N, bs, bo, kappa, act, _p(out[0:]), _p(out[1:]), _p(ws), ws.numel(),
                                                    _lib.current_stream(dev)), "gvf_gaussian_reg_fwd")
         ctx.save_for_backward(scaling, opacity)

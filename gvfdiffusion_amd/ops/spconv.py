@@ -12,6 +12,8 @@ import ctypes
 import torch
 
 from .. import _lib
+from . import _util
+from ._util import stream as _stream
 from .dit_ops import dt_code
 
 _vp, _i, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_float
@@ -30,14 +32,8 @@ _lib.register({
 })
 
 
-def _stream(t):
-    return _lib.current_stream(t.device)
-
-
 def map_workspace_bytes(T: int) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_spconv_map_workspace_bytes(int(T), ctypes.byref(nb)), "gvf_spconv_map_workspace_bytes")
-    return nb.value
+    return _util.workspace_bytes("gvf_spconv_map_workspace_bytes", int(T))
 
 
 def build_neighbor_map(coords: torch.Tensor) -> torch.Tensor:
@@ -48,7 +44,7 @@ def build_neighbor_map(coords: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"spconv: coords must be a non-empty int32 [T,4] tensor, got {coords.dtype} {tuple(coords.shape)}")
     c = coords.contiguous()
     T = int(c.shape[0])
-    ws = torch.empty(map_workspace_bytes(T), dtype=torch.uint8, device=c.device)
+    ws = _util.scratch("gvf_spconv_map_workspace_bytes", c.device, T)
     nbr = torch.empty((T, 27), dtype=torch.int32, device=c.device)
     _lib.check(_lib.lib().gvf_spconv_neighbor_map(_lib.ptr(c), T, _lib.ptr(nbr), _lib.ptr(ws), ws.numel(), _stream(c)), "gvf_spconv_neighbor_map")
     MAP_BUILDS += 1
@@ -56,9 +52,7 @@ def build_neighbor_map(coords: torch.Tensor) -> torch.Tensor:
 
 
 def packed_bytes(cout: int, cin: int) -> int:
-    nb = _sz(0)
-    _lib.check(_lib.lib().gvf_spconv_packed_bytes(int(cout), int(cin), ctypes.byref(nb)), "gvf_spconv_packed_bytes")
-    return nb.value
+    return _util.workspace_bytes("gvf_spconv_packed_bytes", int(cout), int(cin))
 
 
 def pack_weight(w: torch.Tensor, dtype) -> torch.Tensor:

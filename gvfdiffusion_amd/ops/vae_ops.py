@@ -4,6 +4,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from ._util import ptr as _p
 from .dit_ops import dt_code, LP_DTYPES
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
@@ -15,10 +16,6 @@ _lib.register({
     "gvf_geglu": (_i, [_i, _vp, _i, _vp, _i, _i64, _i, _vp]),
     "gvf_vae_embed": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _i, _f, _f, _vp]),
 })
-
-
-def _p(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def geglu_bf16(x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:

@@ -12,9 +12,9 @@ import torch
 
 from .. import _lib
 from . import dit_ops
+from ._util import psz as _psz, ptr as _p, rows16 as _rows16, scratch as _scratch
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
-_psz = ctypes.POINTER(_sz)
 
 _lib.register({
     "gvf_geglu_fwd": (_i, [_i, _vp, _i64, _vp, _i64, _i64, _i, _vp]),
@@ -27,23 +27,13 @@ _lib.register({
     "gvf_posterior_groups_bwd": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i, _vp]),
 })
 
-_p = _lib.ptr
 EMBED_EPS = 1e-5          # nn.LayerNorm's default: the two embedding norms of the reference (the PreNorm norms use 1e-6)
 MAX_QDIM, MAX_C = 16, 768
 
 
-def _workspace(fn_name, dev, *dims):
-    nb = _sz(0)
-    _lib.check(getattr(_lib.lib(), fn_name)(*dims, ctypes.byref(nb)), fn_name)
-    return torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
-
-
-def _rows16(x):
-    """a 2-D 16-bit tensor as the row kernels address it: unit column stride, row stride a multiple of 8 elements, base 16-byte aligned;
-    else a copy -> (tensor, leading dimension)"""
-    if x.stride(1) != 1 or (x.shape[0] > 1 and (x.stride(0) < x.shape[1] or x.stride(0) % 8 != 0)) or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
-    return x, (x.stride(0) if x.shape[0] > 1 else x.shape[1])
+def _row_ld(x):
+    """leading dimension, in elements, of what _rows16 returned"""
+    return x.stride(0) if x.shape[0] > 1 else x.shape[1]
 
 
 # ---- GEGLU ------------------------------------------------------------------------------------------------------------------------------
@@ -51,7 +41,8 @@ class _GegluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u):
         rows, F = u.shape[0], u.shape[1] // 2
-        uv, ldu = _rows16(u)
+        uv = _rows16(u)
+        ldu = _row_ld(uv)
         a = torch.empty((rows, F), dtype=u.dtype, device=u.device)
         if rows > 0:
             _lib.check(_lib.lib().gvf_geglu_fwd(dit_ops.dt_code(u.dtype), _p(uv), ldu, _p(a), F, rows, F, _lib.current_stream(u.device)), "gvf_geglu_fwd")
@@ -65,10 +56,10 @@ class _GegluFn(torch.autograd.Function):
         rows, F = uv.shape[0], uv.shape[1] // 2
         if da.dtype != uv.dtype:
             da = da.to(uv.dtype)
-        dav, ldda = _rows16(da)
+        dav = _rows16(da)
         du = torch.empty((rows, 2 * F), dtype=uv.dtype, device=uv.device)
         if rows > 0:
-            _lib.check(_lib.lib().gvf_geglu_bwd(dit_ops.dt_code(uv.dtype), _p(uv), ctx.ldu, _p(dav), ldda, _p(du), 2 * F, rows, F,
+            _lib.check(_lib.lib().gvf_geglu_bwd(dit_ops.dt_code(uv.dtype), _p(uv), ctx.ldu, _p(dav), _row_ld(dav), _p(du), 2 * F, rows, F,
                                                 _lib.current_stream(uv.device)), "gvf_geglu_bwd")
         return du
 
@@ -111,7 +102,7 @@ class _EmbedFn(torch.autograd.Function):
             de = de.float().contiguous()
         dW, db = torch.empty_like(weight), torch.empty_like(bias)
         dr = torch.empty_like(r) if need[0] else None
-        ws = _workspace("gvf_vae_embed_bwd_workspace_bytes", dev, P, qdim, C)
+        ws = _scratch("gvf_vae_embed_bwd_workspace_bytes", dev, P, qdim, C)
         _lib.check(_lib.lib().gvf_vae_embed_bwd(_p(r), qdim, _p(weight), _p(bias), _p(omega), _p(de), _p(dW), _p(db), _p(dr), P, C, EMBED_EPS,
                                                 _p(ws), ws.numel(), _lib.current_stream(dev)), "gvf_vae_embed_bwd")
         return dr, (dW if need[1] else None), (db if need[2] else None), None
@@ -150,7 +141,7 @@ class _PosteriorGroupsFn(torch.autograd.Function):
         lv, ldl = _ld(logvar)
         z = torch.empty((rows, Dl), dtype=torch.float32, device=dev)
         kl = torch.empty((G,), dtype=torch.float32, device=dev)
-        ws = _workspace("gvf_posterior_groups_workspace_bytes", dev, G, L, Dl)
+        ws = _scratch("gvf_posterior_groups_workspace_bytes", dev, G, L, Dl)
         _lib.check(_lib.lib().gvf_posterior_groups_fwd(_p(mv), ldm, _p(lv), ldl, _p(eps), _p(z), _p(kl), G, L, Dl, _p(ws), ws.numel(),
                                                        _lib.current_stream(dev)), "gvf_posterior_groups_fwd")
         ctx.save_for_backward(mv, lv, eps)

@@ -31,7 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from gvfdiffusion_amd import _lib, synthetic  # noqa: E402
 from gvfdiffusion_amd.model import dit_train  # noqa: E402
 from gvfdiffusion_amd.model.dit import DiT  # noqa: E402
-from gvfdiffusion_amd.ops import dit_ops  # noqa: E402
+from gvfdiffusion_amd.ops import _util, dit_ops  # noqa: E402
 from gvfdiffusion_amd.ops import dit_train as T  # noqa: E402
 import dit_train_ref as R  # noqa: E402
 
@@ -121,7 +121,7 @@ def backward_kernels(B, dt):
     ds, dc, dg = (torch.empty((B, C), device=dev) for _ in range(3))
     qkv, dq = torch.randn((rows, 3 * C), device=dev).to(dt), torch.randn((rows, C), device=dev).to(dt)
     dxq, gamma, dgamma = torch.empty_like(dq), torch.ones((H, D), device=dev), torch.empty((H, D), device=dev)
-    ws = {n: T._workspace(n, dev, *a) for n, a in (("gvf_ln_mod_bwd_workspace_bytes", (rows, C, TN)), ("gvf_gate_residual_bwd_workspace_bytes", (rows, C, TN)),
+    ws = {n: _util.scratch(n, dev, *a) for n, a in (("gvf_ln_mod_bwd_workspace_bytes", (rows, C, TN)), ("gvf_gate_residual_bwd_workspace_bytes", (rows, C, TN)),
                                                    ("gvf_rmsnorm_heads_bwd_workspace_bytes", (rows, H, D)))}
     l, st = _lib.lib(), _lib.current_stream(dev)
     w0, w1, w2 = ws.values()
