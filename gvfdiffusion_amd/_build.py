@@ -77,6 +77,8 @@ SOURCES = {
     "spconv.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     # dense 3x3x3 convolution + occupancy read-out: the spconv.hip flags (1 to 16 accumulators per wave in VGPRs)
     "conv3d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # DINOv2 patch embedding (14x14 stride-14 convolution as an implicit GEMM) + token read-out: the conv3x3.hip flags (4 accumulators per wave in VGPRs)
+    "vit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
 }
 
 

@@ -4,6 +4,8 @@ Reference main() (inference_dpm_latent.py:41-273), and what this script does wit
   :65-66, 177-203  TRELLIS image -> canonical static Gaussians + azimuth alignment   OUT OF SCOPE (image -> 3D generator, needs downloaded
                    weights): the canonical Gaussians come from --static_gs (a .pt list of (P, 14) tensors [xyz3 | rgb3 | op1 | scale3 | rot4],
                    what get_gaussian_tensor returns, train_vae.py:466-472) or are synthetic (--synthetic)
+  (upstream)       scripts/encode_img_cond_dinov2_feature.py:36-64, the DINOv2 features of the condition frames: read from --cond_images, or
+                   computed here from uint8 frames with --cond_frames (gvfdiffusion_amd.utils.encode_cond_frames on the HIP ViT-L/14-reg)
   :74-116          DiT / motion VAE built from the config, checkpoints loaded with the "module." prefix stripped   same; --synthetic draws
                    deterministic weights of the released architectures instead (no checkpoint exists offline)
   :122-125, 142    accelerate, mixed_precision = fp16 if --use_fp16   one process per GPU (torch.distributed.run / accelerate launch set RANK /
@@ -57,6 +59,9 @@ def create_argparser():
     p.add_argument("--synthetic", action="store_true", help="random-init weights of the released architectures, synthetic Gaussians and conditions")
     p.add_argument("--static_gs", type=str, default=None, help=".pt file: list of (P, 14) canonical Gaussian tensors, one per sample")
     p.add_argument("--cond_images", type=str, default=None, help=".pt file: (num_samples, T, 1370, 1024) DINOv2 features")
+    p.add_argument("--cond_frames", type=str, default=None, help=".pt file: uint8 RGB frames (num_samples, T, H, W, 3); encoded here with DINOv2 "
+                   "ViT-L/14-reg (--dinov2_ckpt: its state dict; --synthetic: a random-weight encoder) instead of --cond_images")
+    p.add_argument("--dinov2_ckpt", type=str, default=None, help="state dict of dinov2_vitl14_reg for --cond_frames")
     p.add_argument("--gaussians", type=int, default=32_768, help="--synthetic: Gaussians per sample")
     p.add_argument("--resolution", type=int, default=512, help="render size (the reference forces 512, inference_dpm_latent.py:161-162)")
     p.add_argument("--views", type=int, default=4, help="orbit cameras per timestep (the reference renders 128)")
@@ -110,6 +115,28 @@ def build_models(args, dev, n_copies=1):
     return copies, model_cfg, diff_cfg, vae_cfg
 
 
+_ENCODERS = {}
+
+
+def image_encoder(args, dev):
+    """The DINOv2 ViT-L/14-reg encoder of --cond_frames, one per device: --dinov2_ckpt's weights, or seeded random ones with --synthetic."""
+    if dev not in _ENCODERS:
+        if not (args.dinov2_ckpt or args.synthetic):
+            raise SystemExit("--cond_frames needs --dinov2_ckpt (the released dinov2_vitl14_reg state dict) or --synthetic")
+        from gvfdiffusion_amd.model.dinov2 import dinov2_vitl14_reg
+        enc = dinov2_vitl14_reg(dtype=torch.float16 if args.use_fp16 else torch.bfloat16)
+        if args.dinov2_ckpt:
+            enc.load_state_dict(torch.load(args.dinov2_ckpt, map_location="cpu"), strict=True)
+        else:
+            g = torch.Generator().manual_seed(3)
+            with torch.no_grad():
+                for name, prm in enc.named_parameters():
+                    if prm.dim() >= 2 and "token" not in name and "pos_embed" not in name:
+                        prm.copy_(torch.randn(prm.shape, generator=g) * prm[0].numel() ** -0.5)
+        _ENCODERS[dev] = enc.to(dev)
+    return _ENCODERS[dev]
+
+
 def sample_inputs(args, i, dev, model_cfg):
     """Canonical Gaussians (P, 14) and DINOv2 conditions of global sample i: files if given, else seeded synthetic ones."""
     from gvfdiffusion_amd import synthetic
@@ -120,7 +147,11 @@ def sample_inputs(args, i, dev, model_cfg):
         a = synthetic.random_gaussians(args.gaussians, sh_degree=0, seed=1000 + i)
         gm = synthetic.gaussian_model_from(a, 0, dev)
         gs = torch.cat([gm.get_xyz, gm._features_dc.reshape(-1, 3), gm.get_opacity.reshape(-1, 1), gm.get_scaling, gm.get_rotation], 1).float()
-    if args.cond_images:
+    if args.cond_frames:
+        from gvfdiffusion_amd.utils import encode_cond_frames
+        frames = torch.load(args.cond_frames, map_location="cpu")[i].to(dev)
+        cond = encode_cond_frames(image_encoder(args, dev), frames)[None].float()
+    elif args.cond_images:
         cond = torch.load(args.cond_images, map_location="cpu")[i:i + 1].float().to(dev)
     else:
         cond = torch.randn((1, T, 1370, model_cfg["image_cond_channels"]), generator=torch.Generator().manual_seed(2000 + i)).to(dev)
