@@ -5,7 +5,8 @@ Reference main() (inference_dpm_latent.py:41-273), and what this script does wit
                    weights): the canonical Gaussians come from --static_gs (a .pt list of (P, 14) tensors [xyz3 | rgb3 | op1 | scale3 | rot4],
                    what get_gaussian_tensor returns, train_vae.py:466-472) or are synthetic (--synthetic)
   (upstream)       scripts/encode_img_cond_dinov2_feature.py:36-64, the DINOv2 features of the condition frames: read from --cond_images, or
-                   computed here from uint8 frames with --cond_frames (gvfdiffusion_amd.utils.encode_cond_frames on the HIP ViT-L/14-reg)
+                   computed here from uint8 frames with --cond_frames (gvfdiffusion_amd.utils.encode_cond_frames on the HIP ViT-L/14-reg),
+                   or from RGBA frames with --cond_rgba (utils.preprocess_video_frames / the dataset script's rgb * alpha, on the device)
   :74-116          DiT / motion VAE built from the config, checkpoints loaded with the "module." prefix stripped   same; --synthetic draws
                    deterministic weights of the released architectures instead (no checkpoint exists offline)
   :122-125, 142    accelerate, mixed_precision = fp16 if --use_fp16   one process per GPU (torch.distributed.run / accelerate launch set RANK /
@@ -61,7 +62,12 @@ def create_argparser():
     p.add_argument("--cond_images", type=str, default=None, help=".pt file: (num_samples, T, 1370, 1024) DINOv2 features")
     p.add_argument("--cond_frames", type=str, default=None, help=".pt file: uint8 RGB frames (num_samples, T, H, W, 3); encoded here with DINOv2 "
                    "ViT-L/14-reg (--dinov2_ckpt: its state dict; --synthetic: a random-weight encoder) instead of --cond_images")
-    p.add_argument("--dinov2_ckpt", type=str, default=None, help="state dict of dinov2_vitl14_reg for --cond_frames")
+    p.add_argument("--cond_rgba", type=str, default=None, help=".pt file: uint8 RGBA frames (num_samples, T, H, W, 4), preprocessed on the device "
+                   "(--cond_rgba_route) and encoded as --cond_frames are; excludes --cond_frames and --cond_images")
+    p.add_argument("--cond_rgba_route", type=str, default="wild", choices=["wild", "dataset"], help="wild: the first frame's alpha box, crop, 380 x 380 "
+                   "on a white 512 x 512 canvas (scripts/encode_in_the_wild_img_cond_dinov2_feature.py); dataset: the whole render resized as "
+                   "RGBA and multiplied by its alpha (scripts/encode_img_cond_dinov2_feature.py)")
+    p.add_argument("--dinov2_ckpt", type=str, default=None, help="state dict of dinov2_vitl14_reg for --cond_frames / --cond_rgba")
     p.add_argument("--gaussians", type=int, default=32_768, help="--synthetic: Gaussians per sample")
     p.add_argument("--resolution", type=int, default=512, help="render size (the reference forces 512, inference_dpm_latent.py:161-162)")
     p.add_argument("--views", type=int, default=4, help="orbit cameras per timestep (the reference renders 128)")
@@ -122,7 +128,7 @@ def image_encoder(args, dev):
     """The DINOv2 ViT-L/14-reg encoder of --cond_frames, one per device: --dinov2_ckpt's weights, or seeded random ones with --synthetic."""
     if dev not in _ENCODERS:
         if not (args.dinov2_ckpt or args.synthetic):
-            raise SystemExit("--cond_frames needs --dinov2_ckpt (the released dinov2_vitl14_reg state dict) or --synthetic")
+            raise SystemExit("--cond_frames / --cond_rgba needs --dinov2_ckpt (the released dinov2_vitl14_reg state dict) or --synthetic")
         from gvfdiffusion_amd.model.dinov2 import dinov2_vitl14_reg
         enc = dinov2_vitl14_reg(dtype=torch.float16 if args.use_fp16 else torch.bfloat16)
         if args.dinov2_ckpt:
@@ -137,6 +143,12 @@ def image_encoder(args, dev):
     return _ENCODERS[dev]
 
 
+def check_cond_sources(args):
+    """--cond_rgba is a third source of the condition: it excludes the other two."""
+    if args.cond_rgba and (args.cond_frames or args.cond_images):
+        raise SystemExit("--cond_rgba excludes --cond_frames and --cond_images: give one source of the condition")
+
+
 def sample_inputs(args, i, dev, model_cfg):
     """Canonical Gaussians (P, 14) and DINOv2 conditions of global sample i: files if given, else seeded synthetic ones."""
     from gvfdiffusion_amd import synthetic
@@ -147,7 +159,14 @@ def sample_inputs(args, i, dev, model_cfg):
         a = synthetic.random_gaussians(args.gaussians, sh_degree=0, seed=1000 + i)
         gm = synthetic.gaussian_model_from(a, 0, dev)
         gs = torch.cat([gm.get_xyz, gm._features_dc.reshape(-1, 3), gm.get_opacity.reshape(-1, 1), gm.get_scaling, gm.get_rotation], 1).float()
-    if args.cond_frames:
+    check_cond_sources(args)
+    if args.cond_rgba:
+        from gvfdiffusion_amd.utils import encode_cond_frames, preprocess_video_frames
+        frames = torch.load(args.cond_rgba, map_location="cpu")[i].to(dev)
+        if args.cond_rgba_route == "wild":
+            frames = preprocess_video_frames(frames)[0]
+        cond = encode_cond_frames(image_encoder(args, dev), frames)[None].float()
+    elif args.cond_frames:
         from gvfdiffusion_amd.utils import encode_cond_frames
         frames = torch.load(args.cond_frames, map_location="cpu")[i].to(dev)
         cond = encode_cond_frames(image_encoder(args, dev), frames)[None].float()
@@ -240,6 +259,7 @@ def build_chain(args, dev, probe=None):
 
 def main(argv=None):
     args = create_argparser().parse_args(argv)
+    check_cond_sources(args)
     if not torch.cuda.is_available():
         raise SystemExit("inference_dpm_latent.py needs an MI355X (the package has no CPU path)")
     from gvfdiffusion_amd import distributed as D
