@@ -79,6 +79,8 @@ SOURCES = {
     "conv3d.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     # DINOv2 patch embedding (14x14 stride-14 convolution as an implicit GEMM) + token read-out: the conv3x3.hip flags (4 accumulators per wave in VGPRs)
     "vit.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    # CLIP ViT-B/32 patch embedding (32x32 stride-32 convolution, K staged in chunks), ln_pre and the cosine read-out: the vit.hip flags
+    "clip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     # RGBA preprocessing: the black / white composites are the reference's fp32 / fp64 sequences, the product rounded before the add
     "rgba.hip": ["-ffp-contract=off"],
 }

@@ -305,9 +305,10 @@ __global__ __launch_bounds__(THREADS, BN == 192 ? 3 : (BK == 32 ? 4 : (BM == 64 
             if (row >= M || col0 >= N) continue;
             if (EPI == GVF_EPI_GELU_BF16) { v.x = gelu_tanh(v.x); v.y = gelu_tanh(v.y); v.z = gelu_tanh(v.z); v.w = gelu_tanh(v.w); }
             if (EPI == GVF_EPI_GELU_ERF_16) { v.x = gvf_gelu_erf(v.x); v.y = gvf_gelu_erf(v.y); v.z = gvf_gelu_erf(v.z); v.w = gvf_gelu_erf(v.w); }
+            if (EPI == GVF_EPI_QUICK_GELU_16) { v.x = gvf_quick_gelu(v.x); v.y = gvf_quick_gelu(v.y); v.z = gvf_quick_gelu(v.z); v.w = gvf_quick_gelu(v.w); }
             const size_t o = (size_t)row * ldc + col0;
             if (vec_ok && col0 + 3 < N) {
-                if (EPI == GVF_EPI_STORE_BF16 || EPI == GVF_EPI_GELU_BF16 || EPI == GVF_EPI_GELU_ERF_16) {
+                if (EPI == GVF_EPI_STORE_BF16 || EPI == GVF_EPI_GELU_BF16 || EPI == GVF_EPI_GELU_ERF_16 || EPI == GVF_EPI_QUICK_GELU_16) {
                     uint2 w2;
                     w2.x = LP::pack(v.x, v.y); w2.y = LP::pack(v.z, v.w);
                     *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(Cv) + o) = w2;
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(THREADS, BN == 192 ? 3 : (BK == 32 ? 4 : (BM == 64 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (col0 + e >= N) break;
-                    if (EPI == GVF_EPI_STORE_BF16 || EPI == GVF_EPI_GELU_BF16 || EPI == GVF_EPI_GELU_ERF_16) {
+                    if (EPI == GVF_EPI_STORE_BF16 || EPI == GVF_EPI_GELU_BF16 || EPI == GVF_EPI_GELU_ERF_16 || EPI == GVF_EPI_QUICK_GELU_16) {
                         reinterpret_cast<unsigned short*>(Cv)[o + e] = LP::to16(vv[e]);
                     } else if (EPI == GVF_EPI_STORE_F32) {
                         reinterpret_cast<float*>(Cv)[o + e] = vv[e];
@@ -425,6 +426,7 @@ int launch_gemm(const void* A, int lda, const void* W, int ldw, const float* bia
         case GVF_EPI_STORE_F32: GVF_GEMM_LAUNCH(GVF_EPI_STORE_F32) break;
         case GVF_EPI_RESID_F32: GVF_GEMM_LAUNCH(GVF_EPI_RESID_F32) break;
         case GVF_EPI_GELU_ERF_16: GVF_GEMM_LAUNCH(GVF_EPI_GELU_ERF_16) break;
+        case GVF_EPI_QUICK_GELU_16: GVF_GEMM_LAUNCH(GVF_EPI_QUICK_GELU_16) break;
         default: return GVF_EINVAL;
     }
 #undef GVF_GEMM_LAUNCH

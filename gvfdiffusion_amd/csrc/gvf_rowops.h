@@ -38,6 +38,14 @@ __device__ __forceinline__ float gvf_wave_sum_xor(float v) {
     return v;
 }
 
+// The 16 lanes of a DPP row (lane ^ 1, ^ 2, ^ 4, ^ 8): a 64-column slice of a row held as one float4 per lane (the partial LayerNorm
+// statistics gvf_gemm_ln reads, written by the row kernels of clip.hip).
+__device__ __forceinline__ float gvf_row16_sum_xor(float v) {
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 // ---- sums over a workgroup of THREADS threads; red: LDS scratch ---------------------------------------------------------------------------
 // A fixed tree over the threads (red: THREADS doubles), so a workgroup's partial does not depend on anything but its terms.  Every thread
 // gets the total.
@@ -86,6 +94,11 @@ __device__ __forceinline__ uint4 gvf_pack8(const float (&f)[8]) {
 // ---- GELU, the exact erf form (model/autoencoder.py:90-93) ---------------------------------------------------------------------------------
 // The GEGLU kernels (vae.hip, vae_train.hip) and the GEGLU epilogues of the GEMMs (gemm.hip, gemm8.hip) must agree bit for bit.
 __device__ __forceinline__ float gvf_gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// ---- QuickGELU x * sigmoid(1.702 x) (CLIP's MLP) ---------------------------------------------------------------------------------------------
+// expf, not __expf: the argument reaches +-1e5 for a 16-bit pre-activation.  exp(+large) = inf gives x / inf = -0 (x < 0 there), exp(-large) = 0
+// gives x: finite for every finite x.
+__device__ __forceinline__ float gvf_quick_gelu(float x) { return x / (1.0f + expf(-1.702f * x)); }
 
 // ---- host: argument checks of the C entry points ------------------------------------------------------------------------------------------
 static inline bool gvf_lp_ok(int dtype) { return dtype == GVF_DT_BF16 || dtype == GVF_DT_F16; }

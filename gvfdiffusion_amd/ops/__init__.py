@@ -14,4 +14,5 @@ from . import vae_train  # noqa: F401
 from . import spconv  # noqa: F401
 from . import conv3d  # noqa: F401
 from . import vit  # noqa: F401
+from . import clip  # noqa: F401
 from ..sparse import vox2seq as _vox2seq  # noqa: F401,E402

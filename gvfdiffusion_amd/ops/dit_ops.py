@@ -12,7 +12,7 @@ from ._util import ptr as _p, stream as _stream
 
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
-EPI_STORE_BF16, EPI_GELU_BF16, EPI_STORE_F32, EPI_RESID_F32, EPI_GEGLU_16, EPI_GELU_ERF_16 = 0, 1, 2, 3, 4, 5
+EPI_STORE_BF16, EPI_GELU_BF16, EPI_STORE_F32, EPI_RESID_F32, EPI_GEGLU_16, EPI_GELU_ERF_16, EPI_QUICK_GELU_16 = 0, 1, 2, 3, 4, 5, 6
 EPI_STORE_16, EPI_GELU_16 = EPI_STORE_BF16, EPI_GELU_BF16        # (the 16-bit output takes the call's operand type)
 DT_BF16, DT_F16 = 0, 1
 LP_DTYPES = (torch.bfloat16, torch.float16)

@@ -106,16 +106,22 @@ def _mask_extent(mask: torch.Tensor) -> torch.Tensor:
 
 @torch.no_grad()
 def align_gaussian_to_canonical(static_gs_model, canonical_image, canonical_alpha, intrinsics, static_vae, id, device,
-                                in_the_wild=True, clip_score=None, chunk_frames: int = 60):
+                                in_the_wild=True, clip_score=None, chunk_frames: int = 60, clip_model=None, return_scores: bool = False):
     """Find the azimuth (and the image-space scale) at which the static Gaussians look like the canonical view, then turn
     the model so that this view becomes the front view (utils/inference_utils.py:38-178; same arguments and return value
     `(static_gs_model, best_scale_factor)`).
 
     The reference renders the 360 (or 4) azimuths one at a time and scores each with an L1 term plus 0.2 x (1 - CLIP
     similarity) from a downloaded ViT-B/32.  Here the azimuths are rendered in batches by the alpha-output rasteriser
-    variant, the bounding boxes come from the alpha masks on the device, and the score's CLIP term is a callback:
-    `clip_score(image (3,512,512) in [0,1], canonical_image) -> similarity`; with None (no CLIP weights on this machine) the
-    score is the L1 term alone."""
+    variant, the bounding boxes come from the alpha masks on the device, and the score's CLIP term comes from `clip_model`, a
+    model.clip.CLIPVisionTransformer with the ViT-B/32 weights loaded: the canonical image is encoded once, the 512 x 512 candidates of
+    a render chunk are stacked and scored by ONE batched encoder call, and their similarities come back to the host once per chunk,
+    together with the L1 terms.  `clip_score(image (3,512,512) in [0,1], canonical_image) -> similarity` is the older seam for a
+    model of the caller's own, called once per view; passing both is an error.  With neither the score is the L1 term alone.
+    The choice rule is the reference's in every case: strict `<`, in azimuth order (a NaN score never wins).
+    return_scores=True appends the list of (azimuth, score) of every scored view to the return value."""
+    if clip_model is not None and clip_score is not None:
+        raise ValueError("pass clip_model= (batched, on the device) or clip_score= (a callback per view), not both")
     renderer = static_vae.renderers["MipGS"]
     renderer.pipe.use_mip_gaussian = False                                       # :50
     azimuths = np.arange(-180, 180, 1) if in_the_wild else np.arange(-180, 180, 90)
@@ -124,11 +130,14 @@ def align_gaussian_to_canonical(static_gs_model, canonical_image, canonical_alph
     cmask = (canonical_alpha.to(device) > 0.5)
     canonical_size = int(_mask_extent(cmask[None])[0])
     best = (1e8, 0, 1.0)
+    scores = []
     if canonical_size >= 0:
         K = intrinsics.to(device)
+        canonical_unit = clip_model.unit_feature(canonical_image) if clip_model is not None else None
         for s0 in range(0, len(azimuths), chunk_frames):
             out = renderer.render_frames(static_gs_model, cams[s0:s0 + chunk_frames], K, want_alpha_depth=True)
             sizes = _mask_extent(out.alpha > 0.5).tolist()
+            views, images, l1 = [], [], []
             for k, rendered_size in enumerate(sizes):
                 if rendered_size < 0:
                     continue                                                      # nothing visible from here (:66-67)
@@ -146,17 +155,33 @@ def align_gaussian_to_canonical(static_gs_model, canonical_image, canonical_alph
                     o = (target - 512) // 2
                     image = image[:, o:o + 512, o:o + 512]
                 image = image.clamp(0.0, 1.0)
+                if clip_model is not None:                                        # scored below, the whole chunk at once
+                    views.append((k, scale_factor))
+                    images.append(image)
+                    l1.append((image - canonical_image).abs().mean())
+                    continue
                 diff = float((image - canonical_image).abs().mean())
                 if clip_score is not None:
                     diff += (1.0 - float(clip_score(image, canonical_image))) * 0.2
+                scores.append((int(azimuths[s0 + k]), diff))
                 if diff < best[0]:
                     best = (diff, int(azimuths[s0 + k]), float(scale_factor))
+            if views:
+                sims = clip_model.similarity(torch.stack(images), canonical_unit)
+                host = torch.stack([torch.stack(l1).float(), sims]).tolist()      # the chunk's one read-back
+                for (k, scale_factor), d, sim in zip(views, host[0], host[1]):
+                    diff = d + (1.0 - sim) * 0.2
+                    scores.append((int(azimuths[s0 + k]), diff))
+                    if diff < best[0]:
+                        best = (diff, int(azimuths[s0 + k]), float(scale_factor))
     _, best_azi, best_scale_factor = best
     print(f"\nID: {id} \tBest azimuth: {best_azi} \tBest scale factor: {best_scale_factor}")
     a = math.radians(-best_azi)
     rot = torch.tensor([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]], device=device, dtype=torch.float32)
     static_gs_model.from_xyz((rot @ static_gs_model.get_xyz.T).T)
     static_gs_model.from_rotation(matrix_to_quaternion(rot @ build_rotation(static_gs_model.get_rotation).to(device)))
+    if return_scores:
+        return static_gs_model, best_scale_factor, scores
     return static_gs_model, best_scale_factor
 
 

@@ -37,6 +37,8 @@ extern "C" {
                                     come in 64-row groups of 32 value rows then their 32 gate rows (output column 32 b + i <- rows 64 b + i and
                                     64 b + 32 + i); N % 64 == 0; bit-identical to the store epilogue followed by gvf_geglu */
 #define GVF_EPI_GELU_ERF_16  5   /* C 16-bit [M][ldc] = r16(gelu_erf(acc)): the exact-erf GELU (nn.GELU() of the DINOv2 MLP); gvf_gemm and gvf_gemm_ln only */
+#define GVF_EPI_QUICK_GELU_16 6  /* C 16-bit [M][ldc] = r16(v / (1 + exp(-1.702 v))), v = acc, in fp32: CLIP's QuickGELU x * sigmoid(1.702 x); finite for every
+                                    finite v (exp overflows to inf at large -v and the quotient is -0); gvf_gemm and gvf_gemm_ln only */
 
 /* C = A W^T (+bias): A bf16 [M][lda] row-major, W bf16 [N][ldw] row-major (nn.Linear layout),
  * K a multiple of 32 (pad activations and weights; other K are refused), lda/ldw multiples of 8, bias f32 [N] or null.

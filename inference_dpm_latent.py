@@ -68,6 +68,9 @@ def create_argparser():
                    "on a white 512 x 512 canvas (scripts/encode_in_the_wild_img_cond_dinov2_feature.py); dataset: the whole render resized as "
                    "RGBA and multiplied by its alpha (scripts/encode_img_cond_dinov2_feature.py)")
     p.add_argument("--dinov2_ckpt", type=str, default=None, help="state dict of dinov2_vitl14_reg for --cond_frames / --cond_rgba")
+    p.add_argument("--clip_ckpt", type=str, default=None, help="local file with CLIP ViT-B/32 weights for the alignment score's CLIP term "
+                   "(align_gaussian_to_canonical(..., clip_model=clip_encoder(args, dev))): OpenAI's ViT-B-32.pt (a TorchScript archive) or a "
+                   "state dict (OpenAI `visual.*` names or transformers' CLIPVisionModelWithProjection); never a URL")
     p.add_argument("--gaussians", type=int, default=32_768, help="--synthetic: Gaussians per sample")
     p.add_argument("--resolution", type=int, default=512, help="render size (the reference forces 512, inference_dpm_latent.py:161-162)")
     p.add_argument("--views", type=int, default=4, help="orbit cameras per timestep (the reference renders 128)")
@@ -141,6 +144,27 @@ def image_encoder(args, dev):
                         prm.copy_(torch.randn(prm.shape, generator=g) * prm[0].numel() ** -0.5)
         _ENCODERS[dev] = enc.to(dev)
     return _ENCODERS[dev]
+
+
+_CLIP = {}
+
+
+def clip_encoder(args, dev):
+    """The CLIP ViT-B/32 image tower of the alignment score, one per device, from --clip_ckpt (a local file: nothing is downloaded); None
+    without the flag (the score is then the L1 term alone)."""
+    if not args.clip_ckpt:
+        return None
+    if dev not in _CLIP:
+        if "://" in args.clip_ckpt or not os.path.isfile(args.clip_ckpt):
+            raise SystemExit(f"--clip_ckpt must name a local file, got {args.clip_ckpt!r}")
+        from gvfdiffusion_amd.model.clip import clip_vit_b32, load_clip_state_dict
+        try:                                              # OpenAI's ViT-B-32.pt is a TorchScript archive
+            sd = torch.jit.load(args.clip_ckpt, map_location="cpu").state_dict()
+        except RuntimeError:
+            sd = torch.load(args.clip_ckpt, map_location="cpu")
+        enc = load_clip_state_dict(clip_vit_b32(dtype=torch.float16), sd)          # fp16 operands, as the reference's clip.load on a GPU
+        _CLIP[dev] = enc.to(dev)
+    return _CLIP[dev]
 
 
 def check_cond_sources(args):
